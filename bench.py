@@ -2,7 +2,13 @@
 """Headline benchmark: upsampled query-points/s on the BASELINE.json config
 "Synthetic sphere 5000 pts, 4x upsample, M=48 T=4, 1xMI355X".
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure (the strong-scaling
+pass, the roofline / kNN / M=100 / reference-default legs, the CPU baseline, the all-gather alone) runs only with --full.
+--dump-outputs DIR: after the timed steps, the last step's outputs (what Generator3D6.refine hands its caller) are written as
+DIR/refined.npy (f64 [n,3], gathered over the ranks), DIR/normals.npy (f32 [n,3]) and DIR/distances.npy (f32 [n]) — rank 0's
+shard for the last two.  The inputs are fixed (seeded cloud, queries and weights), so two builds can be compared output for output.
 
 N > 1: one process per GPU over RCCL.  Started by ``torch.distributed.run`` (RANK / WORLD_SIZE in the environment) the
 ranks run directly; started as a plain command, this process spawns ``python -m torch.distributed.run --nproc-per-node N``
@@ -15,10 +21,10 @@ outer kNN + gather/centre -> fn forward -> normalise -> gather/rotate -> fd forw
 (+ for N > 1 the all-gather of the refined points).  Inputs (cloud, queries, weights) are in HBM
 before the timed region.  Weak scaling (default, the BASELINE workload): every rank refines its own 4096 queries per
 step.  --scaling strong: a step = the whole 385 582-seed cloud of the same sphere (its real dense-grid seeds), sharded
-contiguously over the ranks, one all-gather of the refined cloud per step; the default run also times one such pass as
-the extra object "strong_scaling" so that the driver's N = 1, 2, 4, 8 runs give a strong-scaling curve too.
+contiguously over the ranks, one all-gather of the refined cloud per step; a --full run in the weak mode also times one such
+pass as the extra object "strong_scaling" so that N = 1, 2, 4, 8 runs give a strong-scaling curve too.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      the dominant kernel (fn_edge_chain_kernel<512, 12, .>: block 3 of fn, its whole per-edge chain fn/snn_coder.py:355-389
                 in one launch), launched alone through its C-ABI entry between two events on the current stream: achieved =
                 issued f16 MFMA TFLOP/s against the 2.5 PFLOP/s dense peak; beside it SURVEY.md 8(d)'s fp32-MFMA model figure,
@@ -321,6 +327,22 @@ def spawn_ranks(args):
 
 
 STRONG_CLOUD_SPACING = 0.004        # generation.py:69 default dense_spacing -> 385 582 seeds on the N=5000 sphere
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: each output of the last step as out_dir/<name>.npy (f64 stays f64, the rest f32).  Were the files to exceed
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows (sorted) is written from every output instead."""
+    arrays = {k: v.detach().cpu().numpy() for k, v in outputs.items()}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[0] for a in arrays.values())
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, n * DUMP_LIMIT_BYTES // total), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def main():
@@ -334,7 +356,14 @@ def main():
     ap.add_argument("--no-strong-leg", action="store_true", help="skip the extra whole-cloud pass of the weak mode")
     ap.add_argument("--no-m100", action="store_true", help="skip the secondary M=100 figure")
     ap.add_argument("--no-ref-default", action="store_true", help="skip the figure at the reference's default configuration (M=100, fn T=6, fd T=7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (strong-scaling pass, roofline / kNN / M=100 / reference-default legs, "
+                         "CPU baseline, all-gather alone); the --no-* switches above prune them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (refined, normals, distances) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -374,27 +403,31 @@ def main():
     cloud = torch.as_tensor(cloud_host, device=dev)
     seeds = torch.as_tensor(T.grid_queries(B_PER_GPU * world, 0)[rank * B_PER_GPU:(rank + 1) * B_PER_GPU], device=dev)
     strong = args.scaling == "strong"
-    want_strong_leg = strong or not args.no_strong_leg
+    want_strong_leg = strong or (args.full and not args.no_strong_leg)
     all_seeds = None
     if want_strong_leg:       # the cloud's real seeds (in-process dense grid flood, same on every rank), resident before timing
         # every rank floods the same cloud before the timed region: share the host's cores between the ranks of the node
         os.environ.setdefault("SAPCU_SEED_THREADS", str(min(16, max(1, (os.cpu_count() or 16) // max(1, world)))))
         all_seeds = torch.as_tensor(sgen.dense_seeds(cloud_host, STRONG_CLOUD_SPACING), device=dev)
 
+    last = {}             # the latest step's outputs, as refine() hands them to its caller (for --dump-outputs)
+
     def weak_step():
         with torch.no_grad():
-            refined, _, _ = gen.refine(cloud, seeds)
+            refined, normals, dists = gen.refine(cloud, seeds)
             if use_pg:
                 refined = sdist.gather_refined(refined, B_PER_GPU * world)   # the one collective of the path
+        last.update(refined=refined, normals=normals, distances=dists)
         return refined
 
     def strong_step():
         n = all_seeds.shape[0]
         s, e = sdist.shard_range(n, rank, world)
         with torch.no_grad():
-            refined, _, _ = gen.refine(cloud, all_seeds[s:e])
+            refined, normals, dists = gen.refine(cloud, all_seeds[s:e])
             if use_pg:
                 refined = sdist.gather_refined(refined, n)
+        last.update(refined=refined, normals=normals, distances=dists)
         return refined
 
     step = strong_step if strong else weak_step
@@ -470,7 +503,10 @@ def main():
     per_step = all_seeds.shape[0] if strong else B_PER_GPU * world
     log("timed %d steps: %.1f ms/step (per rank, own time: %.1f .. %.1f ms/step)"
         % (args.steps, dt / args.steps * 1e3, spread[0] / args.steps * 1e3, spread[1] / args.steps * 1e3))
-    allgather_us = allgather_alone(per_step) if use_pg else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
+    allgather_us = allgather_alone(per_step) if use_pg and args.full else None
 
     strong_leg = None
     if want_strong_leg and not strong:
@@ -514,12 +550,13 @@ def main():
         if use_pg:
             import torch.distributed as dist
             line["collective_backend"] = dist.get_backend()
-            # the record explains itself: the collective alone, and each rank's own step time (before it waits for the others)
-            line["allgather_us"] = allgather_us
+            # the record explains itself: the collective alone (--full), and each rank's own step time (before it waits for the others)
+            if allgather_us is not None:
+                line["allgather_us"] = allgather_us
             line["rank_ms_per_step"] = {"min": round(spread[0] / args.steps * 1e3, 3), "max": round(spread[1] / args.steps * 1e3, 3)}
         if strong_leg:
             line["strong_scaling"] = strong_leg
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             line["roofline"] = roofline_leg(dev)
             log("roofline leg done: %s" % line["roofline"])
             line["knn_kernel"] = knn_leg(dev, cloud, seeds)
@@ -529,7 +566,7 @@ def main():
             if not args.no_ref_default:
                 line["ref_default"] = ref_default_leg(dev, cloud, seeds)
                 log("reference-default leg: %s" % line["ref_default"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sdn, sdd)
             log("cpu baseline done: %s" % line["cpu_baseline"])
     barrier()

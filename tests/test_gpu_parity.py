@@ -2171,14 +2171,14 @@ def test_bench_gpus_1_takes_the_rccl_branch_when_asked():
 
 @pytest.mark.gpu
 def test_bench_gpus_2_as_a_plain_command_rehearsal():
-    """`python bench.py --gpus 2` (no launcher around it) spawns its two ranks itself; on this one-GPU box that is a
+    """`python bench.py --gpus 2 --full` (no launcher around it) spawns its two ranks itself; on this one-GPU box that is a
     rehearsal (both ranks on cuda:0, gloo) — exit code 0 and ONE JSON line with n_gpus 2 and the strong-scaling leg."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SAPCU_BENCH_REHEARSE")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-roofline"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -2186,6 +2186,34 @@ def test_bench_gpus_2_as_a_plain_command_rehearsal():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["rehearsal"] is True and line["scaling"] == "weak" and line["value"] > 0
     assert line["strong_scaling"]["seeds"] == 385582 and line["strong_scaling"]["n_gpus"] == 2
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the plain run times exactly the steps asked for,
+    carries none of the --full legs, and writes the last step's refined points, normals and distances — the refined points
+    being the queries displaced by exactly those normals and distances."""
+    import json
+    import subprocess
+    import sys
+    from sapcu_amd import testing as T
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SAPCU_BENCH_REHEARSE", "SAPCU_BENCH_NCCL1")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    for extra in ("strong_scaling", "roofline", "knn_kernel", "m100", "ref_default", "cpu_baseline"):
+        assert extra not in line, extra
+    refined, normals, dists = (np.load(str(tmp_path / (n + ".npy"))) for n in ("refined", "normals", "distances"))
+    assert refined.dtype == np.float64 and refined.shape == (4096, 3)
+    assert normals.dtype == np.float32 and normals.shape == (4096, 3)
+    assert dists.dtype == np.float32 and dists.shape == (4096,)
+    assert np.isfinite(refined).all() and np.isfinite(normals).all() and np.isfinite(dists).all()
+    assert np.array_equal(refined, G.displace(T.grid_queries(4096, 0), normals, dists))
 
 
 # ---------------------------------------------------------------------------------------------
