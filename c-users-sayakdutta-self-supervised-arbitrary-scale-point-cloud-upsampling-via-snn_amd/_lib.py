@@ -34,6 +34,11 @@ _SIGNATURES = {
     "sapcu_knn_gather_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sapcu_gather_rotate_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "sapcu_displace_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sapcu_knn_grid_workspace_bytes": (c_int64, [c_int64]),
+    "sapcu_knn_self_grid_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int64,
+                                        POINTER(c_int64), c_void_p]),
+    "sapcu_outlier_stats_f64": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sapcu_outlier_keep_f64": (c_int, [c_void_p, c_int64, c_double, c_double, c_void_p, c_void_p]),
     "sapcu_fps_workspace_bytes": (c_int64, [c_int64]),
     "sapcu_fps_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "sapcu_dense_seeds_host": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int64, POINTER(c_int64)]),

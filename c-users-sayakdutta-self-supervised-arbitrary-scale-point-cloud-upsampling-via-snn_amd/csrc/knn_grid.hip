@@ -1,0 +1,597 @@
+// Exact kNN of a point set against itself on a uniform cell grid, and the outlier filter's statistics in numpy's
+// summation order.  Replaces the brute-force kNN-30 + the two np.mean of the reference's generation.py:176-183.
+//
+// kNN (knn_self_grid_kernel):
+//   * the grid is built on the device: bounding box (block partials, one finishing thread), cell keys
+//     key = (cz*gy + cy)*gx + cx with c = floor((p - origin) / h) clamped to the grid, counting sort (integer atomics
+//     for the counts, a three-kernel exclusive scan, integer atomics for the slots) into a cell-ordered SoA copy
+//     x|y|z plus the original indices.  The order inside a cell is arbitrary: the (distance, index) keys decide;
+//   * one query per wavefront (4 per 256-thread workgroup).  The running top-k is the sorted list of knn_outer.hip,
+//     distributed across the lanes (entry p in lane p, k <= 64); candidates arrive in cell order, not index order, so
+//     a candidate is compared on the key (d, i) — a point at the k-th distance with a lower index still enters;
+//   * the search visits Chebyshev shells r = 0, 1, 2, ... around the query's cell.  A shell row whose y or z offset
+//     is +-r is ONE contiguous range of the sorted points (the cells of a row are consecutive keys); the other rows
+//     contribute their two end cells.  After shell r the distance from the query to the faces of the visited block,
+//     less a slack far above the rounding of the cell keys and of the faces, bounds every unvisited point from below;
+//     the search stops only when that bound squared (shrunk by 1e-9) is STRICTLY above the current k-th squared
+//     distance — a point whose rounded distance ties the k-th cannot be skipped.  Correct for any cell size;
+//   * the squared distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 operations, the output
+//     distance sqrt_cr of it: bit for bit the arithmetic and the order of knn_outer.hip;
+//   * non-finite or huge (|x| > 1e150) coordinates, and n < KNN_GRID_MIN_N with the automatic cell size, run the
+//     brute-force kernel of knn_outer.hip instead (the launcher reads the grid parameters back: one stream sync).
+//
+// Statistics (outlier_stats_kernel, outlier_keep_kernel): numpy 2.x np.mean of a C-contiguous f64 [n,kk] table —
+//   * the row mean is the pairwise leaf of kk <= 128 values (8 accumulators over the first kk - kk%8 values, combined
+//     ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the rest added in order; fewer than 8: a plain sum from 0) over kk;
+//   * the global sum is the flattened table cut into chunks of `bufsize` elements (np.getbufsize()), each summed by
+//     numpy's recursive pairwise sum (split at n/2 rounded down to a multiple of 8, leaves <= 128 as above); the chunk
+//     sums are added in sequence from 0.0 by the caller (sapcu_amd/generation.py), since they may come from several ranks.
+#include "common.h"
+
+namespace sapcu {
+
+constexpr int KNN_GRID_WAVES = 4;
+constexpr int KNN_GRID_BBOX_BLOCKS = 256;
+constexpr int64_t KNN_GRID_MIN_N = 4096;     // below this (automatic cell size) the brute force costs less than a grid build
+constexpr int SCAN_TILE = 1024;              // 256 threads x 4 counts
+constexpr int STATS_MAX_LEAVES = 512;        // a chunk of <= STATS_MAX_BUFSIZE elements has <= 129 pairwise leaves
+constexpr int64_t STATS_MAX_BUFSIZE = 16384;
+
+struct GridParams {
+    double ox, oy, oz;       // origin = bounding-box minimum
+    double h;                // cell edge
+    double slack;            // absolute margin on the face distances (>> the rounding of keys and faces)
+    int gx, gy, gz;
+    int fallback;            // 1: brute force (non-finite / huge coordinates)
+};
+
+static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+static inline int64_t grid_cell_cap(int64_t n) { return 2 * n + 64; }
+
+struct GridWs {
+    double* partials;        // [KNN_GRID_BBOX_BLOCKS][8]: min xyz, max xyz, bad flag
+    GridParams* params;
+    int* start;              // [cells + 1]: counts, then exclusive prefix sums
+    int* cursor;             // [cells]
+    int* tile_sums;          // [ceil((cells + 1) / SCAN_TILE)]
+    int* key;                // [n]
+    double* sx;              // [n] each, cell order
+    double* sy;
+    double* sz;
+    int* sidx;               // [n] original index of each sorted point
+    size_t bytes;
+};
+
+static GridWs grid_ws_layout(void* base, int64_t n) {
+    const int64_t cap = grid_cell_cap(n);
+    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    char* p = (char*)base;
+    size_t off = 0;
+    GridWs w;
+    auto take = [&](size_t b) {
+        char* r = p ? p + off : nullptr;
+        off += align256(b);
+        return r;
+    };
+    w.partials = (double*)take(sizeof(double) * 8 * KNN_GRID_BBOX_BLOCKS);
+    w.params = (GridParams*)take(sizeof(GridParams));
+    w.start = (int*)take(sizeof(int) * (cap + 1));
+    w.cursor = (int*)take(sizeof(int) * cap);
+    w.tile_sums = (int*)take(sizeof(int) * tiles);
+    w.key = (int*)take(sizeof(int) * n);
+    w.sx = (double*)take(sizeof(double) * n);
+    w.sy = (double*)take(sizeof(double) * n);
+    w.sz = (double*)take(sizeof(double) * n);
+    w.sidx = (int*)take(sizeof(int) * n);
+    w.bytes = off;
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------------ grid build
+__global__ __launch_bounds__(256) void grid_bbox_kernel(const double* __restrict__ pts, int64_t n, double* __restrict__ partials) {
+    const double INF = __builtin_huge_val();
+    double lx = INF, ly = INF, lz = INF, hx = -INF, hy = -INF, hz = -INF, bad = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+        if (!(fabs(x) <= 1e150 && fabs(y) <= 1e150 && fabs(z) <= 1e150)) bad = 1.0;    // NaN, inf, or a square that could overflow
+        lx = fmin(lx, x);
+        ly = fmin(ly, y);
+        lz = fmin(lz, z);
+        hx = fmax(hx, x);
+        hy = fmax(hy, y);
+        hz = fmax(hz, z);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lx = fmin(lx, __shfl_xor(lx, o));
+        ly = fmin(ly, __shfl_xor(ly, o));
+        lz = fmin(lz, __shfl_xor(lz, o));
+        hx = fmax(hx, __shfl_xor(hx, o));
+        hy = fmax(hy, __shfl_xor(hy, o));
+        hz = fmax(hz, __shfl_xor(hz, o));
+        bad = fmax(bad, __shfl_xor(bad, o));
+    }
+    __shared__ double red[4][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wave][0] = lx;
+        red[wave][1] = ly;
+        red[wave][2] = lz;
+        red[wave][3] = hx;
+        red[wave][4] = hy;
+        red[wave][5] = hz;
+        red[wave][6] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const int c = threadIdx.x;
+        double v = red[0][c];
+        for (int w = 1; w < 4; ++w) v = c < 3 ? fmin(v, red[w][c]) : fmax(v, red[w][c]);
+        partials[blockIdx.x * 8 + c] = v;
+    }
+}
+
+// one thread: the bounding box, the cell edge (given or automatic) and the grid dimensions, at most `cap` cells
+__global__ void grid_setup_kernel(const double* __restrict__ partials, int k, int64_t n, double cell_size, int64_t cap,
+                                  GridParams* __restrict__ prm) {
+    if (threadIdx.x != 0) return;
+    const double INF = __builtin_huge_val();
+    double lx = INF, ly = INF, lz = INF, hx = -INF, hy = -INF, hz = -INF, bad = 0.0;
+    for (int b = 0; b < KNN_GRID_BBOX_BLOCKS; ++b) {
+        const double* q = partials + b * 8;
+        lx = fmin(lx, q[0]);
+        ly = fmin(ly, q[1]);
+        lz = fmin(lz, q[2]);
+        hx = fmax(hx, q[3]);
+        hy = fmax(hy, q[4]);
+        hz = fmax(hz, q[5]);
+        bad = fmax(bad, q[6]);
+    }
+    GridParams p;
+    p.fallback = bad != 0.0;
+    p.ox = lx;
+    p.oy = ly;
+    p.oz = lz;
+    p.gx = p.gy = p.gz = 1;
+    p.h = 1.0;
+    p.slack = 0.0;
+    if (!p.fallback) {
+        const double ex = hx - lx, ey = hy - ly, ez = hz - lz;
+        const double emax = fmax(ex, fmax(ey, ez));
+        // surfaces: about 2k points per cell face of (longest extent)^2 / n — the k nearest then mostly lie in shell 1
+        double h = cell_size > 0.0 ? cell_size : emax * sqrt(2.0 * k / (double)n);
+        if (!(emax > 0.0)) h = 1.0;                                  // every point equal: one cell
+        h = fmax(h, emax * 1e-9);                                    // floor(extent / h) stays far inside int range
+        double gx, gy, gz;
+        for (;;) {
+            gx = floor(ex / h) + 1.0;
+            gy = floor(ey / h) + 1.0;
+            gz = floor(ez / h) + 1.0;
+            if (gx * gy * gz <= (double)cap) break;
+            h *= 1.125;
+        }
+        p.h = h;
+        p.gx = (int)gx;
+        p.gy = (int)gy;
+        p.gz = (int)gz;
+        const double amax = fmax(fmax(fmax(fabs(lx), fabs(hx)), fmax(fabs(ly), fabs(hy))), fmax(fabs(lz), fabs(hz)));
+        p.slack = 1e-11 * (amax + emax + h);
+    }
+    *prm = p;
+}
+
+__device__ __forceinline__ int grid_coord(double v, double o, double h, int g) {
+    const double t = floor(__ddiv_rn(__dsub_rn(v, o), h));
+    return t < 0.0 ? 0 : (t >= (double)(g - 1) ? g - 1 : (int)t);
+}
+
+__global__ __launch_bounds__(256) void grid_count_kernel(const double* __restrict__ pts, int64_t n, const GridParams* __restrict__ prm,
+                                                         int* __restrict__ count, int* __restrict__ key) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const GridParams p = *prm;
+    const int cx = grid_coord(pts[i * 3 + 0], p.ox, p.h, p.gx);
+    const int cy = grid_coord(pts[i * 3 + 1], p.oy, p.h, p.gy);
+    const int cz = grid_coord(pts[i * 3 + 2], p.oz, p.h, p.gz);
+    const int c = (cz * p.gy + cy) * p.gx + cx;
+    key[i] = c;
+    atomicAdd(&count[c], 1);
+}
+
+// exclusive scan of the int counts in tiles of SCAN_TILE: per-tile sums, a one-workgroup scan of those, per-tile apply
+__device__ __forceinline__ int block_excl_scan256(int v, int* red4, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) red4[wave] = x;
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += red4[w];
+    *total = red4[0] + red4[1] + red4[2] + red4[3];
+    __syncthreads();
+    return off + x - v;
+}
+
+__global__ __launch_bounds__(256) void scan_tile_sum_kernel(const int* __restrict__ a, int64_t m, int* __restrict__ tile_sums) {
+    __shared__ int red4[4];
+    const int64_t b = (int64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (b + j < m) s += a[b + j];
+    int total;
+    block_excl_scan256(s, red4, &total);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void scan_tile_offsets_kernel(int* __restrict__ tile_sums, int64_t tiles) {
+    __shared__ int red4[4];
+    int carry = 0;
+    for (int64_t base = 0; base < tiles; base += 256) {
+        const int64_t t = base + threadIdx.x;
+        const int v = t < tiles ? tile_sums[t] : 0;
+        int total;
+        const int ex = block_excl_scan256(v, red4, &total);
+        if (t < tiles) tile_sums[t] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(256) void scan_apply_kernel(int* __restrict__ a, int64_t m, const int* __restrict__ tile_off) {
+    __shared__ int red4[4];
+    const int64_t b = (int64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
+    int v0 = b + 0 < m ? a[b + 0] : 0;
+    int v1 = b + 1 < m ? a[b + 1] : 0;
+    int v2 = b + 2 < m ? a[b + 2] : 0;
+    int v3 = b + 3 < m ? a[b + 3] : 0;
+    int total;
+    const int run = block_excl_scan256(v0 + v1 + v2 + v3, red4, &total) + tile_off[blockIdx.x];
+    if (b + 0 < m) a[b + 0] = run;
+    if (b + 1 < m) a[b + 1] = run + v0;
+    if (b + 2 < m) a[b + 2] = run + v0 + v1;
+    if (b + 3 < m) a[b + 3] = run + v0 + v1 + v2;
+}
+
+__global__ __launch_bounds__(256) void grid_scatter_kernel(const double* __restrict__ pts, int64_t n, const int* __restrict__ key,
+                                                           int* __restrict__ cursor, double* __restrict__ sx, double* __restrict__ sy,
+                                                           double* __restrict__ sz, int* __restrict__ sidx) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int slot = atomicAdd(&cursor[key[i]], 1);
+    sx[slot] = pts[i * 3 + 0];
+    sy[slot] = pts[i * 3 + 1];
+    sz[slot] = pts[i * 3 + 2];
+    sidx[slot] = (int)i;
+}
+
+// --------------------------------------------------------------------------------------------------------- search
+// the cross-lane moves of knn_outer.hip's list: DPP wave_shr:1 (lane 0 keeps its own) and v_readlane
+__device__ __forceinline__ int grid_shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ double grid_shr1_d(double v) {
+    return __hiloint2double(grid_shr1_i(__double2hiint(v)), grid_shr1_i(__double2loint(v)));
+}
+__device__ __forceinline__ double grid_readlane_d(double v, int lane_uniform) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform),
+                            __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
+}
+
+struct GridList {
+    double d;         // this lane's entry of the sorted list (squared distance, point index)
+    int i;
+    double tau_d;     // entry k-1 (wave-uniform)
+    int tau_i;
+};
+
+// every point of the sorted range [a, b) against the list
+__device__ __forceinline__ void grid_scan_range(GridList& L, int a, int b, double qx, double qy, double qz,
+                                                const double* __restrict__ sx, const double* __restrict__ sy,
+                                                const double* __restrict__ sz, const int* __restrict__ sidx, int k, int lane) {
+    const double INF = __builtin_huge_val();
+    for (int off = a; off < b; off += 64) {
+        const int j = off + lane;
+        double d = INF;
+        int pi = 0x7fffffff;
+        if (j < b) {
+            const double dx = __dsub_rn(qx, sx[j]);
+            const double dy = __dsub_rn(qy, sy[j]);
+            const double dz = __dsub_rn(qz, sz[j]);
+            d = __dmul_rn(dx, dx);
+            d = __dadd_rn(d, __dmul_rn(dy, dy));
+            d = __dadd_rn(d, __dmul_rn(dz, dz));
+            pi = sidx[j];
+        }
+        unsigned long long mask = __ballot(j < b && (d < L.tau_d || (d == L.tau_d && pi < L.tau_i)));
+        while (mask) {
+            const int src = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const double cd = grid_readlane_d(d, src);
+            const int ci = __builtin_amdgcn_readlane(pi, src);
+            if (!(cd < L.tau_d || (cd == L.tau_d && ci < L.tau_i))) continue;
+            // position = number of entries below the candidate's key; entries at and above it move up one lane
+            const int pos = __popcll(__ballot(L.d < cd || (L.d == cd && L.i < ci)));
+            const double ud = grid_shr1_d(L.d);
+            const int ui = grid_shr1_i(L.i);
+            if (lane == pos) {
+                L.d = cd;
+                L.i = ci;
+            } else if (lane > pos) {
+                L.d = ud;
+                L.i = ui;
+            }
+            L.tau_d = grid_readlane_d(L.d, k - 1);
+            L.tau_i = __builtin_amdgcn_readlane(L.i, k - 1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void knn_self_grid_kernel(const double* __restrict__ pts, int64_t row0, int64_t row1, int k,
+                                                            const GridParams* __restrict__ prm, const int* __restrict__ start,
+                                                            const double* __restrict__ sx, const double* __restrict__ sy,
+                                                            const double* __restrict__ sz, const int* __restrict__ sidx,
+                                                            int64_t* __restrict__ idx_out, double* __restrict__ dist_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t qi = row0 + (int64_t)blockIdx.x * KNN_GRID_WAVES + (threadIdx.x >> 6);
+    if (qi >= row1) return;                                            // wave-uniform
+    const GridParams p = *prm;
+    const double qx = pts[qi * 3 + 0], qy = pts[qi * 3 + 1], qz = pts[qi * 3 + 2];
+    const int cx = grid_coord(qx, p.ox, p.h, p.gx);
+    const int cy = grid_coord(qy, p.oy, p.h, p.gy);
+    const int cz = grid_coord(qz, p.oz, p.h, p.gz);
+    const double INF = __builtin_huge_val();
+    GridList L{INF, 0x7fffffff, INF, 0x7fffffff};
+    const int rmax = max(max(p.gx, p.gy), p.gz);
+    for (int r = 0; r <= rmax; ++r) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
+        for (int z = z0; z <= z1; ++z) {
+            for (int y = y0; y <= y1; ++y) {
+                const int row = (z * p.gy + y) * p.gx;
+                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {        // a face row of the shell: its whole x range
+                    grid_scan_range(L, start[row + x0], start[row + x1 + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
+                } else {                                                            // an inner row: its two end cells
+                    if (cx - r >= 0)
+                        grid_scan_range(L, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
+                    if (cx + r < p.gx)
+                        grid_scan_range(L, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
+                }
+            }
+        }
+        // lower bound for every point outside the visited block [c-r, c+r]^3 (a side at the grid's edge has none)
+        double bnd = INF;
+        if (cx - r > 0) bnd = fmin(bnd, __dsub_rn(qx, __dadd_rn(p.ox, __dmul_rn((double)(cx - r), p.h))));
+        if (cx + r < p.gx - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.ox, __dmul_rn((double)(cx + r + 1), p.h)), qx));
+        if (cy - r > 0) bnd = fmin(bnd, __dsub_rn(qy, __dadd_rn(p.oy, __dmul_rn((double)(cy - r), p.h))));
+        if (cy + r < p.gy - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oy, __dmul_rn((double)(cy + r + 1), p.h)), qy));
+        if (cz - r > 0) bnd = fmin(bnd, __dsub_rn(qz, __dadd_rn(p.oz, __dmul_rn((double)(cz - r), p.h))));
+        if (cz + r < p.gz - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oz, __dmul_rn((double)(cz + r + 1), p.h)), qz));
+        if (bnd == INF) break;                                               // the whole grid is visited
+        bnd = __dsub_rn(bnd, p.slack);
+        if (bnd > 0.0 && __dmul_rn(__dmul_rn(bnd, bnd), 1.0 - 1e-9) > L.tau_d) break;
+    }
+    if (lane < k) {
+        const int64_t o = (qi - row0) * k + lane;
+        idx_out[o] = L.i;
+        dist_out[o] = sqrt_cr(L.d);
+    }
+}
+
+int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row1, int k, double cell_size, int64_t* idx,
+                         double* dist, void* ws, int64_t ws_bytes, int64_t* info, hipStream_t st) {
+    if (info) info[0] = info[1] = info[2] = info[3] = 0;
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return SAPCU_OK;
+    if (cell_size == 0.0 && n < KNN_GRID_MIN_N)
+        return launch_knn_outer(pts, n, pts + row0 * 3, rows, k, idx, dist, nullptr, st);
+    GridWs w = grid_ws_layout(ws, n);
+    SAPCU_CHECK_ARG(ws && (int64_t)w.bytes <= ws_bytes, "knn_self_grid: workspace of %lld bytes, need %lld",
+                    (long long)ws_bytes, (long long)w.bytes);
+    hipLaunchKernelGGL(grid_bbox_kernel, dim3(KNN_GRID_BBOX_BLOCKS), dim3(256), 0, st, pts, n, w.partials);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, w.partials, k, n, cell_size, grid_cell_cap(n), w.params);
+    SAPCU_CHECK_LAUNCH();
+    GridParams hp;
+    SAPCU_CHECK_HIP(hipMemcpyAsync(&hp, w.params, sizeof(hp), hipMemcpyDeviceToHost, st));
+    SAPCU_CHECK_HIP(hipStreamSynchronize(st));
+    if (hp.fallback)
+        return launch_knn_outer(pts, n, pts + row0 * 3, rows, k, idx, dist, nullptr, st);
+    if (info) {
+        info[0] = 1;
+        info[1] = hp.gx;
+        info[2] = hp.gy;
+        info[3] = hp.gz;
+    }
+    const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
+    const int64_t m = cells + 1;
+    const int64_t tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    SAPCU_CHECK_HIP(hipMemsetAsync(w.start, 0, sizeof(int) * m, st));
+    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.params, w.start, w.key);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_tile_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, w.start, m, w.tile_sums);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(256), 0, st, w.tile_sums, tiles);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, st, w.start, m, w.tile_sums);
+    SAPCU_CHECK_LAUNCH();
+    SAPCU_CHECK_HIP(hipMemcpyAsync(w.cursor, w.start, sizeof(int) * cells, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(grid_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.key, w.cursor, w.sx, w.sy, w.sz, w.sidx);
+    SAPCU_CHECK_LAUNCH();
+    const int64_t grid = (rows + KNN_GRID_WAVES - 1) / KNN_GRID_WAVES;
+    hipLaunchKernelGGL(knn_self_grid_kernel, dim3((unsigned)grid), dim3(256), 0, st, pts, row0, row1, k, w.params, w.start,
+                       w.sx, w.sy, w.sz, w.sidx, idx, dist);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------- statistics
+// numpy's pairwise leaf (n <= 128)
+__device__ __forceinline__ double np_leaf_sum(const double* __restrict__ a, int n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res = __dadd_rn(res, a[i]);
+        return res;
+    }
+    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+    int i = 8;
+    for (; i < n - (n % 8); i += 8) {
+        r0 = __dadd_rn(r0, a[i + 0]);
+        r1 = __dadd_rn(r1, a[i + 1]);
+        r2 = __dadd_rn(r2, a[i + 2]);
+        r3 = __dadd_rn(r3, a[i + 3]);
+        r4 = __dadd_rn(r4, a[i + 4]);
+        r5 = __dadd_rn(r5, a[i + 5]);
+        r6 = __dadd_rn(r6, a[i + 6]);
+        r7 = __dadd_rn(r7, a[i + 7]);
+    }
+    double res = __dadd_rn(__dadd_rn(__dadd_rn(r0, r1), __dadd_rn(r2, r3)), __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
+    for (; i < n; ++i) res = __dadd_rn(res, a[i]);
+    return res;
+}
+
+// 64-thread workgroups.  Blocks [0, nchunks): the pairwise sum of one `bufsize`-element chunk of the flattened table (lane 0
+// lays the leaves out in LDS, the lanes sum them, lane 0 folds them back up the tree with an LDS stack); the blocks after
+// those: the row means, one row per thread.
+__global__ __launch_bounds__(64) void outlier_stats_kernel(const double* __restrict__ dist, int64_t rows, int kk, int64_t bufsize,
+                                                          int64_t nchunks, double* __restrict__ row_mean, double* __restrict__ chunk_sum) {
+    if ((int64_t)blockIdx.x >= nchunks) {
+        const int64_t r = ((int64_t)blockIdx.x - nchunks) * 64 + threadIdx.x;
+        if (r < rows) row_mean[r] = __ddiv_rn(np_leaf_sum(dist + r * kk, kk), (double)kk);
+        return;
+    }
+    __shared__ int leaf_o[STATS_MAX_LEAVES], leaf_l[STATS_MAX_LEAVES];
+    __shared__ double leaf_s[STATS_MAX_LEAVES];
+    __shared__ int st_o[64], st_l[64], st_e[64];
+    __shared__ double vs[64];
+    __shared__ int nleaves;
+    const int64_t total = rows * (int64_t)kk;
+    const int64_t c0 = (int64_t)blockIdx.x * bufsize;
+    const int len = (int)((total - c0) < bufsize ? (total - c0) : bufsize);
+    const double* a = dist + c0;
+    if (threadIdx.x == 0) {
+        int sp = 0, nl = 0;
+        st_o[sp] = 0;
+        st_l[sp] = len;
+        ++sp;
+        while (sp > 0) {
+            --sp;
+            const int o = st_o[sp], l = st_l[sp];
+            if (l <= 128) {
+                leaf_o[nl] = o;
+                leaf_l[nl] = l;
+                ++nl;
+            } else {
+                int n2 = l / 2;
+                n2 -= n2 % 8;
+                st_o[sp] = o + n2;                 // the right half pushed first: the left one is popped (and numbered) first
+                st_l[sp] = l - n2;
+                ++sp;
+                st_o[sp] = o;
+                st_l[sp] = n2;
+                ++sp;
+            }
+        }
+        nleaves = nl;
+    }
+    __syncthreads();
+    const int nl = nleaves;
+    for (int j = threadIdx.x; j < nl; j += 64) leaf_s[j] = np_leaf_sum(a + leaf_o[j], leaf_l[j]);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    // post-order: a node is pushed unexpanded (e = 0); popped, an inner node goes back expanded (e = 1) under its two halves
+    int sp = 0, vsp = 0, leaf = 0;
+    st_l[sp] = len;
+    st_e[sp] = 0;
+    ++sp;
+    while (sp > 0) {
+        --sp;
+        const int l = st_l[sp];
+        if (st_e[sp]) {
+            const double rhs = vs[--vsp];
+            const double lhs = vs[--vsp];
+            vs[vsp++] = __dadd_rn(lhs, rhs);
+        } else if (l <= 128) {
+            vs[vsp++] = leaf_s[leaf++];
+        } else {
+            int n2 = l / 2;
+            n2 -= n2 % 8;
+            st_l[sp] = l;
+            st_e[sp] = 1;
+            ++sp;
+            st_l[sp] = l - n2;
+            st_e[sp] = 0;
+            ++sp;
+            st_l[sp] = n2;
+            st_e[sp] = 0;
+            ++sp;
+        }
+    }
+    chunk_sum[blockIdx.x] = vs[0];
+}
+
+__global__ __launch_bounds__(256) void outlier_keep_kernel(const double* __restrict__ row_mean, int64_t rows, double mean,
+                                                           double threshold, uint8_t* __restrict__ keep) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    keep[i] = row_mean[i] < __dmul_rn(mean, threshold) ? 1 : 0;
+}
+
+int launch_outlier_stats(const double* dist, int64_t rows, int kk, int64_t bufsize, double* row_mean, double* chunk_sum,
+                         hipStream_t st) {
+    if (rows == 0) return SAPCU_OK;
+    const int64_t nchunks = (rows * kk + bufsize - 1) / bufsize;
+    const int64_t rblocks = (rows + 63) / 64;
+    hipLaunchKernelGGL(outlier_stats_kernel, dim3((unsigned)(nchunks + rblocks)), dim3(64), 0, st, dist, rows, kk, bufsize, nchunks,
+                       row_mean, chunk_sum);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+int launch_outlier_keep(const double* row_mean, int64_t rows, double mean, double threshold, uint8_t* keep, hipStream_t st) {
+    if (rows == 0) return SAPCU_OK;
+    hipLaunchKernelGGL(outlier_keep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, row_mean, rows, mean, threshold,
+                       keep);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+}  // namespace sapcu
+
+// ================================================================================== C ABI
+using namespace sapcu;
+
+extern "C" {
+
+int64_t sapcu_knn_grid_workspace_bytes(int64_t n) { return n < 1 ? -1 : (int64_t)grid_ws_layout(nullptr, n).bytes; }
+
+int sapcu_knn_self_grid_f64(const double* pts, int64_t n, int64_t row0, int64_t row1, int k, double cell_size, int64_t* idx_out,
+                            double* dist_out, void* workspace, int64_t workspace_bytes, int64_t* info_host, void* stream) {
+    SAPCU_CHECK_ARG(pts && ((idx_out && dist_out) || row1 == row0), "knn_self_grid: null pointer");     // an empty range writes nothing
+    SAPCU_CHECK_ARG(n >= 1 && n <= (1LL << 29), "knn_self_grid: need 1 <= n <= 2^29 (n=%lld)", (long long)n);
+    SAPCU_CHECK_ARG(k >= 1 && k <= 64 && k <= n, "knn_self_grid: need 1 <= k <= min(64, n) (n=%lld k=%d)", (long long)n, k);
+    SAPCU_CHECK_ARG(0 <= row0 && row0 <= row1 && row1 <= n, "knn_self_grid: bad row range [%lld, %lld) of %lld",
+                    (long long)row0, (long long)row1, (long long)n);
+    SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "knn_self_grid: cell_size must be finite and >= 0");
+    return launch_knn_self_grid(pts, n, row0, row1, k, cell_size, idx_out, dist_out, workspace, workspace_bytes, info_host,
+                                (hipStream_t)stream);
+}
+
+int sapcu_outlier_stats_f64(const double* dist, int64_t rows, int kk, int64_t bufsize, double* row_mean_out, double* chunk_sum_out,
+                            void* stream) {
+    SAPCU_CHECK_ARG(rows >= 0 && kk >= 1 && kk <= 128, "outlier_stats: need rows >= 0 and 1 <= kk <= 128");
+    SAPCU_CHECK_ARG(bufsize >= 1 && bufsize <= STATS_MAX_BUFSIZE, "outlier_stats: bufsize must be in 1..%lld (got %lld)",
+                    (long long)STATS_MAX_BUFSIZE, (long long)bufsize);
+    SAPCU_CHECK_ARG(rows == 0 || (dist && row_mean_out && chunk_sum_out), "outlier_stats: null pointer");
+    return launch_outlier_stats(dist, rows, kk, bufsize, row_mean_out, chunk_sum_out, (hipStream_t)stream);
+}
+
+int sapcu_outlier_keep_f64(const double* row_mean, int64_t rows, double mean, double threshold, uint8_t* keep_out, void* stream) {
+    SAPCU_CHECK_ARG(rows >= 0 && (rows == 0 || (row_mean && keep_out)), "outlier_keep: bad argument");
+    return launch_outlier_keep(row_mean, rows, mean, threshold, keep_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

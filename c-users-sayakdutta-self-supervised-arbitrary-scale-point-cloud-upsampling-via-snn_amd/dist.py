@@ -14,6 +14,7 @@ bit for bit; sharded runs therefore use ``knn_cache_mode='fresh'`` (stated in DE
 """
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -107,3 +108,117 @@ def upsample_sharded(generator, cloud_dev, seeds_dev, group=None):
         if old is not None:
             model.knn_cache_mode = old
     return gather_refined(local, n, group), (s, e)
+
+
+# -- the whole cloud across ranks: seeds -> sharded refine -> sharded outlier filter (-> FPS) ---------------------------------
+# Every rank returns what Generator3D6.upsample returns in one process with knn_cache_mode='fresh', bit for bit: the seeds are
+# flooded once on rank 0 and broadcast, the refine is upsample_sharded, and the outlier filter's rows are cut into blocks that
+# hold whole chunks of np.mean (generation.outlier_row_align), so that the chunk sums of all ranks, gathered in rank order, are
+# the single-process chunk sums.  Collectives: two broadcasts (seed count, seeds), the refine's all-gather, one all-gather of the
+# chunk sums and one of the keep mask.  gloo moves host tensors, nccl (RCCL) device tensors, as in gather_refined.
+
+def outlier_row_ranges(n, world, kk=None, bufsize=None):
+    """[(start, end)] of every rank's rows of the outlier filter over n points: contiguous, in rank order, each start and each
+    end but n a multiple of bufsize / gcd(kk, bufsize) rows (4096 for kk = 30 and numpy's default buffer); equal numbers of
+    whole blocks per rank, so ranks past the last block get empty ranges."""
+    from . import generation
+    kk = min(generation.OUTLIER_K, n) if kk is None else kk
+    align = generation.outlier_row_align(kk, bufsize)
+    blocks = -(-n // align)
+    per = -(-blocks // world)
+    return [(min(n, r * per * align), min(n, (r + 1) * per * align)) for r in range(world)]
+
+
+def _src0(group):
+    return 0 if group is None else dist.get_global_rank(group, 0)
+
+
+def _comm_device(group, dev):
+    return torch.device("cpu") if dist.get_backend(group) == "gloo" else dev
+
+
+def broadcast_seeds(generator, data, group=None):
+    """The seeds of cloud ``data`` [N,3], flooded ONCE on the group's rank 0 (``generator._dense_seeds``: the in-process
+    generator with all its host threads) and broadcast — the count, then the array.  Returns f64 [n,3] on generator.device."""
+    rank = dist.get_rank(group)
+    dev = torch.device(generator.device)
+    cdev = _comm_device(group, dev)
+    seeds = None
+    if rank == 0:
+        seeds = torch.from_numpy(np.ascontiguousarray(generator._dense_seeds(data), dtype=np.float64).reshape(-1, 3))
+    count = torch.tensor([seeds.shape[0] if rank == 0 else 0], dtype=torch.int64, device=cdev)
+    dist.broadcast(count, src=_src0(group), group=group)
+    n = int(count.item())
+    buf = seeds.to(cdev) if rank == 0 else torch.empty((n, 3), dtype=torch.float64, device=cdev)
+    if n:
+        dist.broadcast(buf, src=_src0(group), group=group)
+    return buf.to(dev)
+
+
+def _all_gather_rows(local, counts, group=None):
+    """All-gather of per-rank row blocks whose sizes ``counts`` every rank knows -> their concatenation in rank order."""
+    world = len(counts)
+    per = max(counts)
+    dev = local.device
+    if local.is_cuda and dist.get_backend(group) == "gloo":
+        local = local.cpu()
+    padded = local.new_zeros((per,) + tuple(local.shape[1:]))
+    padded[: local.shape[0]] = local
+    out = local.new_empty((world * per,) + tuple(local.shape[1:]))
+    dist.all_gather_into_tensor(out, padded.contiguous(), group=group)
+    return torch.cat([out[r * per: r * per + counts[r]] for r in range(world)]).to(dev)
+
+
+def upsample_cloud_sharded(generator, data, group=None):
+    """``generator.upsample(data)`` over the ranks of ``group``: every rank returns the same filtered ndarray [M',3] f64, bit for
+    bit the single-process result with ``knn_cache_mode='fresh'`` (the sharded refine needs it; see upsample_sharded)."""
+    from . import generation
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    data = np.squeeze(data, 0) if np.ndim(data) == 3 else np.asarray(data)
+    seeds_dev = broadcast_seeds(generator, data, group)
+    n = seeds_dev.shape[0]
+    if n == 0:                              # nothing in the distance band (Generator3D6.upsample_seeds)
+        return np.zeros((0, 3), dtype=np.float64)
+    cloud_dev = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64), device=generator.device)
+    kk = min(generation.OUTLIER_K, n)
+    bufsize = np.getbufsize()
+    ranges = outlier_row_ranges(n, world, kk, bufsize)
+    chunks = [generation.outlier_chunk_count(e - s, kk, bufsize) for s, e in ranges]
+    with torch.no_grad():
+        refined, _ = upsample_sharded(generator, cloud_dev, seeds_dev, group)
+        keep_local, _ = generator.outlier_filter_rows(refined, ranges[rank], lambda sums: _all_gather_rows(sums, chunks, group))
+        keep = _all_gather_rows(keep_local.to(torch.uint8), [e - s for s, e in ranges], group)
+    generator.check_numeric_guards()
+    return refined.cpu().numpy()[keep.cpu().numpy().astype(bool)]
+
+
+def process_cloud_sharded(cloud, generator, target_points, group=None):
+    """``pipeline.process_cloud`` on top of upsample_cloud_sharded: every rank returns the same [target_points, 3] FPS output."""
+    from . import pipeline
+    return pipeline._process_cloud_with(cloud, lambda d: upsample_cloud_sharded(generator, d, group), generator.device,
+                                         target_points)
+
+
+def process_files_sharded(inputs, outputs, generator, target_points, group=None):
+    """generate.py's loop over a directory of clouds (BASELINE config 4) across ranks: file i goes to rank i % world, which
+    writes outputs[i] with ``pipeline.process_file``; no collective but the closing barrier.  The files are refined with
+    ``knn_cache_mode='fresh'`` (a rank's cache history differs from one process's), so each output is byte-identical to
+    process_file's in that mode.  Returns the indices of the files this rank processed.  A rank whose file fails still reaches
+    the barrier (it is in a ``finally``), so the other ranks are released and the error is raised on that rank alone."""
+    from . import pipeline
+    if len(inputs) != len(outputs):
+        raise ValueError("process_files_sharded: %d inputs but %d outputs" % (len(inputs), len(outputs)))
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    mine = list(range(rank, len(inputs), world))
+    model = generator.model1
+    old = getattr(model, "knn_cache_mode", None)
+    if old is not None:
+        model.knn_cache_mode = "fresh"
+    try:
+        for i in mine:
+            pipeline.process_file(inputs[i], outputs[i], generator, target_points)
+    finally:
+        if old is not None:
+            model.knn_cache_mode = old
+        dist.barrier(group=group)
+    return mine

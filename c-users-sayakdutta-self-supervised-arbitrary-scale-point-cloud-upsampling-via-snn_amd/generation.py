@@ -16,6 +16,7 @@ Seed generation (generation.py:112-118: the ``./dense`` subprocess and its text 
 the GPU hot path; ``upsample`` generates the seeds in process (csrc/dense_seeds.cpp:
 same seeds, same order), ``upsample_seeds`` takes a seed array directly.
 """
+import math
 import os
 
 import numpy as np
@@ -69,6 +70,113 @@ def knn_gather(cloud_dev, queries_dev, k, want_dist=False, want_patch=True):
         _lib.check(lib.sapcu_knn_gather_f64(_lib.ptr(cloud_dev), n, _lib.ptr(queries_dev), b, k, _lib.ptr(idx),
                                             _lib.ptr(dist), _lib.ptr(patch), _lib.current_stream()))
     return idx, dist, patch
+
+
+def knn_self_grid(pts_dev, k, rows=None, cell_size=0.0, info=None):
+    """Exact kNN of rows [row0, row1) of a point set f64 [n,3] against the whole set on a device cell grid
+    (csrc/knn_grid.hip): (idx int64 [rows,k], dist f64 [rows,k]), bit for bit ``knn_gather(pts, pts[row0:row1], k,
+    want_dist=True)``.  k <= 64; ``cell_size`` 0 = automatic (any value gives the same result).  ``info``, a list, receives
+    [1 if the grid ran else 0 (brute force), gx, gy, gz].  Synchronises the current stream once (the grid size is read back)."""
+    import ctypes
+    lib = _lib.load()
+    n = pts_dev.shape[0]
+    r0, r1 = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
+    if k > n:
+        raise ValueError("k must be less than or equal to the number of training points (k=%d, N=%d)" % (k, n))
+    pts_dev = pts_dev.contiguous()
+    dev = pts_dev.device
+    idx = torch.empty((r1 - r0, k), dtype=torch.int64, device=dev)
+    dist = torch.empty((r1 - r0, k), dtype=torch.float64, device=dev)
+    nbytes = int(lib.sapcu_knn_grid_workspace_bytes(n))
+    ws = torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)
+    out = (ctypes.c_int64 * 4)()
+    with torch.cuda.device(dev):
+        _lib.check(lib.sapcu_knn_self_grid_f64(_lib.ptr(pts_dev), n, r0, r1, k, float(cell_size), _lib.ptr(idx), _lib.ptr(dist),
+                                               _lib.ptr(ws), nbytes, out, _lib.current_stream()))
+    if info is not None:
+        info[:] = list(out)
+    return idx, dist
+
+
+# -- the kNN-30 outlier filter on the device (generation.py:176-183).  Its keep decision is the f64 comparison
+#    mean(row) < mean(all) * threshold, rounded as numpy 2.x's np.mean rounds (csrc/knn_grid.hip: row means = numpy's pairwise
+#    leaf; the global sum = pairwise sums of np.getbufsize()-element chunks of the flattened [n, kk] table, added in sequence).
+OUTLIER_K = 30
+
+
+def outlier_row_align(kk, bufsize=None):
+    """Rows per aligned block: a row range starting on a multiple of it (and ending on one, or at n) holds whole chunks of np.mean."""
+    bufsize = np.getbufsize() if bufsize is None else int(bufsize)
+    return bufsize // math.gcd(max(int(kk), 1), bufsize)
+
+
+def outlier_chunk_count(rows, kk, bufsize=None):
+    """Number of np.mean chunks in `rows` rows of a [*, kk] table that start on a chunk boundary."""
+    bufsize = np.getbufsize() if bufsize is None else int(bufsize)
+    return -(-int(rows) * int(kk) // bufsize)
+
+
+def outlier_stats_device(dist_dev, bufsize=None):
+    """(row means f64 [rows], chunk sums f64 [chunks]) of a distance table f64 [rows, kk] on the device, in numpy's order."""
+    lib = _lib.load()
+    bufsize = np.getbufsize() if bufsize is None else int(bufsize)
+    dist_dev = dist_dev.contiguous()
+    rows, kk = dist_dev.shape
+    mean = torch.empty((rows,), dtype=torch.float64, device=dist_dev.device)
+    sums = torch.empty((outlier_chunk_count(rows, kk, bufsize),), dtype=torch.float64, device=dist_dev.device)
+    with torch.cuda.device(dist_dev.device):
+        _lib.check(lib.sapcu_outlier_stats_f64(_lib.ptr(dist_dev), rows, kk, bufsize, _lib.ptr(mean), _lib.ptr(sums),
+                                               _lib.current_stream()))
+    return mean, sums
+
+
+def outlier_global_mean(chunk_sums, count):
+    """np.mean's total: the chunk sums (all of them, in order) added in sequence from 0.0 on the host, over the element count."""
+    total = 0.0
+    for s in chunk_sums.tolist():
+        total += s
+    return total / count
+
+
+def outlier_keep_device(row_mean_dev, mean, threshold):
+    """Device bool mask row_mean < mean * threshold (f64 product)."""
+    lib = _lib.load()
+    keep = torch.empty(row_mean_dev.shape, dtype=torch.bool, device=row_mean_dev.device)
+    with torch.cuda.device(row_mean_dev.device):
+        _lib.check(lib.sapcu_outlier_keep_f64(_lib.ptr(row_mean_dev), row_mean_dev.shape[0], float(mean), float(threshold),
+                                              _lib.ptr(keep), _lib.current_stream()))
+    return keep
+
+
+def outlier_filter_range(n, rows, bufsize=None):
+    """Checked (start, end) of a row range of the outlier filter over n points: an empty range, or one whose start and end
+    (unless end = n) are multiples of ``outlier_row_align(min(30, n))`` rows — then it holds whole chunks of np.mean."""
+    r0, r1 = int(rows[0]), int(rows[1])
+    align = outlier_row_align(min(OUTLIER_K, n), bufsize)
+    if not (0 <= r0 <= r1 <= n) or (r1 > r0 and (r0 % align or (r1 % align and r1 != n))):
+        raise ValueError("outlier filter: rows [%d, %d) of %d are not aligned to %d-row blocks" % (r0, r1, n, align))
+    return r0, r1
+
+
+def outlier_filter_device(pts_dev, threshold, rows=None, gather_sums=None):
+    """Keep mask of the kNN-30 outlier filter (generation.py:176-183) computed on the device: bool [n] on the device, equal to
+    ``Generator3D6.outlier_filter``'s host result.
+
+    For a row range ``rows = (start, end)`` (checked by ``outlier_filter_range``; may be empty) only those rows are searched:
+    returns (keep bool [end-start] on the device, this range's chunk sums).  ``gather_sums(local_sums)`` must return the chunk
+    sums of ALL rows in order (e.g. an all-gather over ranks, sapcu_amd/dist.py) and is called for an empty range too; without
+    it the range must be all rows."""
+    n = pts_dev.shape[0]
+    kk = min(OUTLIER_K, n)
+    bufsize = np.getbufsize()
+    r0, r1 = (0, n) if rows is None else outlier_filter_range(n, rows, bufsize)
+    if gather_sums is None and (r0, r1) != (0, n):
+        raise ValueError("outlier_filter_device: a part of the rows needs gather_sums (the global mean covers every row)")
+    _, dist = knn_self_grid(pts_dev, kk, (r0, r1))
+    row_mean, sums = outlier_stats_device(dist, bufsize)
+    all_sums = sums if gather_sums is None else gather_sums(sums)
+    keep = outlier_keep_device(row_mean, outlier_global_mean(all_sums.cpu(), n * kk), threshold)
+    return keep if rows is None else (keep, sums)
 
 
 def gather_rotate(cloud_dev, queries_dev, idx, normals):
@@ -203,9 +311,17 @@ class Generator3D6(object):
             if hasattr(m, "gate_violations") and m.gate_violations():
                 raise RuntimeError("%s: refractory gate found open at t >= 1 (%d events)" % (name, m.gate_violations()))
 
+    # -- the outlier filter (generation.py:176-183).  "host" (default): the kNN on the outer-kNN kernel, both means in numpy on
+    #    the host.  "device": outlier_filter_device — grid kNN and the means in numpy's order on the device, the same keep set.
+    outlier_filter_impl = "host"
+
     def outlier_filter(self, pts_dev):
         """Keep points whose mean distance to their 30 nearest (self included) is below
         outlier_threshold x the global mean (generation.py:176-183)."""
+        if self.outlier_filter_impl == "device":
+            return outlier_filter_device(pts_dev, self.outlier_threshold).cpu().numpy()
+        if self.outlier_filter_impl != "host":
+            raise ValueError("outlier_filter_impl must be 'host' or 'device' (got %r)" % (self.outlier_filter_impl,))
         kk = min(30, pts_dev.shape[0])
         _, dist, _ = knn_gather(pts_dev, pts_dev, kk, want_dist=True, want_patch=False)
         # the two means are host numpy on purpose: they decide membership by a float64 comparison and
@@ -213,6 +329,10 @@ class Generator3D6(object):
         dist = dist.cpu().numpy()
         keep = np.mean(dist, axis=1) < np.mean(dist) * self.outlier_threshold
         return keep
+
+    def outlier_filter_rows(self, pts_dev, rows, gather_sums):
+        """One rank's aligned rows of the device outlier filter (sapcu_amd/dist.py): (keep bool [rows] on the device, chunk sums)."""
+        return outlier_filter_device(pts_dev, self.outlier_threshold, rows, gather_sums)
 
     def upsample_seeds(self, data, seeds, return_unfiltered=False):
         cloud_dev = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64), device=self.device)

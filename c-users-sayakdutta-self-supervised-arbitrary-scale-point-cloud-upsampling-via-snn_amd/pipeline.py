@@ -57,13 +57,18 @@ def farthest_point_sample(xyz, npoint, device="cuda"):
 
 def process_cloud(cloud, generator, target_points):
     """generate.py:81-99 without the files: cloud [N,>=3] -> ndarray [target_points,3] float64."""
+    return _process_cloud_with(cloud, generator.upsample, generator.device, target_points)
+
+
+def _process_cloud_with(cloud, upsample, device, target_points):
+    """process_cloud's body around any ``upsample(cloud[None])`` (sapcu_amd/dist.py passes the sharded one)."""
     cloud = np.asarray(cloud)[:, :3]
     cloud, loc, scale = normalize_pointcloud(cloud)
-    upsampled = np.array(generator.upsample(np.expand_dims(cloud, 0)))
+    upsampled = np.array(upsample(np.expand_dims(cloud, 0)))
     upsampled = upsampled * scale + loc
     assert upsampled.shape[0] >= target_points, \
         "Generated %d points, expected >= %d" % (upsampled.shape[0], target_points)
-    indices = farthest_point_sample(upsampled, target_points, device=generator.device)
+    indices = farthest_point_sample(upsampled, target_points, device=device)
     return upsampled[indices]
 
 

@@ -66,6 +66,33 @@ int sapcu_gather_rotate_f64(const double* cloud, int64_t n, const double* querie
 int sapcu_displace_f64(const double* queries, const float* normals, const float* dist, int64_t b,
                        double* out, void* stream);
 
+/* kNN-30 outlier filter (generation.py:176-183) on the device.
+ *
+ * Exact kNN of rows [row0, row1) of a point set pts [n,3] f64 against the whole set on a uniform cell grid built on the
+ * device (csrc/knn_grid.hip): idx_out [row1-row0, k] int64 and dist_out [row1-row0, k] f64, bit for bit what
+ * sapcu_knn_gather_f64 returns for cloud = pts, queries = pts + 3*row0 with a dist_out (same arithmetic, ascending
+ * (distance, index)).  1 <= k <= min(64, n), n <= 2^29.  cell_size: the cell edge, 0 = automatic; any value gives the
+ * same result.  Non-finite or |x| > 1e150 coordinates, and n < 4096 with cell_size 0, take the brute-force kernel.
+ * The workspace holds sapcu_knn_grid_workspace_bytes(n) bytes.  info_host (HOST int64[4], may be NULL) receives
+ * {1 = grid used / 0 = brute force, gx, gy, gz}.  Synchronises `stream` once (the grid size is read back).  An empty
+ * range (row0 == row1) launches nothing and may pass NULL outputs. */
+int64_t sapcu_knn_grid_workspace_bytes(int64_t n);
+int sapcu_knn_self_grid_f64(const double* pts, int64_t n, int64_t row0, int64_t row1, int k, double cell_size,
+                            int64_t* idx_out, double* dist_out, void* workspace, int64_t workspace_bytes,
+                            int64_t* info_host, void* stream);
+
+/* np.mean of a C-contiguous distance table dist [rows, kk] f64 (1 <= kk <= 128), in numpy 2.x's summation order:
+ * row_mean_out [rows] = np.mean(dist, axis=1) bit for bit, and chunk_sum_out [ceil(rows*kk / bufsize)] = the pairwise
+ * sums of the flattened table's bufsize-element chunks (bufsize = np.getbufsize(), 1..16384).  np.mean(dist) is then
+ * (((0.0 + s_0) + s_1) + ...) / (rows*kk) — added by the caller, so that the chunks may come from several ranks: a row
+ * block of a larger table whose first element is a multiple of bufsize has the same chunks as the whole table there. */
+int sapcu_outlier_stats_f64(const double* dist, int64_t rows, int kk, int64_t bufsize, double* row_mean_out,
+                            double* chunk_sum_out, void* stream);
+
+/* keep_out[i] = row_mean[i] < mean * threshold (f64 product), as 0 / 1 bytes. */
+int sapcu_outlier_keep_f64(const double* row_mean, int64_t rows, double mean, double threshold, uint8_t* keep_out,
+                           void* stream);
+
 /* Farthest-point sampling of the refined cloud down to the target count — generate.py:56-74
  * (`farthest_point_sample`): f32 points, start index n/2, running minimum of the squared distance
  * ((dx^2+dy^2)+dz^2, separately rounded) to the chosen set, arg-max with ties to the smallest index.

@@ -1,5 +1,9 @@
 #!/usr/bin/env python3
-"""Whole-cloud run of generate.py's per-cloud body (seeds in process -> hot path -> outlier filter -> FPS to 4N), stage-timed."""
+"""Whole-cloud run of generate.py's per-cloud body (seeds in process -> hot path -> outlier filter -> FPS to 4N), stage-timed.
+
+A second line times the outlier filter's two forms on the same refined cloud (host: brute-force kNN + numpy means; device:
+grid kNN + numpy-order means on the device, generation.outlier_filter_device) and the two kNN-30 kernels alone (grid vs
+knn_outer brute force), best of five after a warm-up, and checks that the keep masks and the kNN tables are equal."""
 import os
 import sys
 import time
@@ -47,6 +51,30 @@ def main():
               n, seeds.shape[0], t1 - t0, t3 - t2, seeds.shape[0] / (t3 - t2), t4 - t3, t5 - t4, target, t7 - t6, out.shape[0],
               np.linalg.norm(out, axis=1).mean(), np.linalg.norm(out, axis=1).std()))
     assert np.unique(picked).shape[0] == target
+
+    def best(f, reps=5):
+        f()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t = time.perf_counter()
+            r = f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t)
+        return min(ts), r
+
+    with torch.no_grad():
+        m = refined.shape[0]
+        t_host, keep_h = best(lambda: g.outlier_filter(refined))
+        t_dev, keep_d = best(lambda: gen.outlier_filter_device(refined, g.outlier_threshold).cpu().numpy())
+        t_grid, (gi, gd) = best(lambda: gen.knn_self_grid(refined, 30))
+        t_brute, (bi, bd, _) = best(lambda: gen.knn_gather(refined, refined, 30, want_dist=True, want_patch=False))
+        info = []
+        gen.knn_self_grid(refined, 30, info=info)
+    assert np.array_equal(keep_h, keep_d) and torch.equal(gi, bi) and torch.equal(gd, bd)
+    print("outlier filter on %d refined points: host %.1f ms | device %.1f ms (keep masks equal) | kNN-30 alone: grid %.2f ms "
+          "(%d x %d x %d cells) vs knn_outer brute force %.2f ms (tables equal)" % (
+              m, 1e3 * t_host, 1e3 * t_dev, 1e3 * t_grid, info[1], info[2], info[3], 1e3 * t_brute))
 
 
 if __name__ == "__main__":
