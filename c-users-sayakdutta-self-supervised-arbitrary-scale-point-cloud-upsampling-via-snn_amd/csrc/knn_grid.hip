@@ -576,6 +576,7 @@ int sapcu_knn_self_grid_f64(const double* pts, int64_t n, int64_t row0, int64_t 
     SAPCU_CHECK_ARG(0 <= row0 && row0 <= row1 && row1 <= n, "knn_self_grid: bad row range [%lld, %lld) of %lld",
                     (long long)row0, (long long)row1, (long long)n);
     SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "knn_self_grid: cell_size must be finite and >= 0");
+    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "knn_self_grid: the workspace must be 8-byte aligned (f64 tables)");
     return launch_knn_self_grid(pts, n, row0, row1, k, cell_size, idx_out, dist_out, workspace, workspace_bytes, info_host,
                                 (hipStream_t)stream);
 }

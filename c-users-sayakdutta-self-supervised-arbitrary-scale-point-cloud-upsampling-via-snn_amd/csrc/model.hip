@@ -703,6 +703,7 @@ int sapcu_fps_f32(const float* xyz, int64_t n, int64_t npoint, int64_t* idx_out,
                     (long long)n, (long long)npoint);
     if (npoint == 0) return SAPCU_OK;
     SAPCU_CHECK_ARG(xyz && idx_out && workspace, "fps: null pointer");
+    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "fps: the workspace must be 8-byte aligned (64-bit mailboxes)");
     if (workspace_bytes < (int64_t)fps_workspace_bytes((int)npoint)) {
         set_error("fps: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
                   (long long)fps_workspace_bytes((int)npoint));
@@ -772,6 +773,10 @@ int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, in
     SAPCU_CHECK_ARG(a && w && c && r >= 0 && n >= 1, "gemm: bad argument");
     SAPCU_CHECK_ARG(!lif4 || lif_steps >= 1, "gemm: lif_steps must be >= 1");
     SAPCU_CHECK_ARG(!(a_split_rows || c_split_rows) || w16_ws, "gemm: split rows need the split-f16 kernels (w16_ws)");
+    // the documented contract (include/sapcu.h), checked here for every kernel: the launchers below check what their own loads need
+    SAPCU_CHECK_ARG(r == 0 || (k > 0 && k % 32 == 0 && lda >= k && ldc >= n), "gemm: need k %% 32 == 0, lda >= k and ldc >= n (k=%d lda=%d n=%d ldc=%d)", k, lda, n, ldc);
+    SAPCU_CHECK_ARG(r == 0 || ((((uintptr_t)a | (uintptr_t)w | (uintptr_t)w16_ws) & 15) == 0 && lda % (a_split_rows ? 8 : 4) == 0),
+                    "gemm: A, W and w16_ws must be 16-byte aligned, lda %% 4 == 0 (%% 8 for split rows) (lda=%d)", lda);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.a = a; g.r = r; g.k = k; g.lda = lda; g.w = w; g.n = n; g.bias = bias; g.c = c; g.ldc = ldc;
@@ -797,13 +802,17 @@ int sapcu_posenc_gemm_f32(const float* pe1, int64_t r, int d, const float* w, co
     SAPCU_CHECK_ARG(pe1 && w && lif4 && qkv && idx && pe_out && attn_in_out && edge_table_ws && r >= 0 && d >= 32 &&
                         lif_steps >= 1 && kk >= 1 && m_pts >= 1,
                     "posenc_gemm: bad argument");
+    // every refusal comes before the first launch (the edge table below is already a kernel that writes edge_table_ws)
+    SAPCU_CHECK_ARG(!split_rows || w16_ws, "posenc_gemm: split rows need the split-f16 kernels (w16_ws)");
+    SAPCU_CHECK_ARG(d % 32 == 0, "posenc_gemm: d=%d must be a multiple of 32", d);
+    SAPCU_CHECK_ARG((((uintptr_t)pe1 | (uintptr_t)w | (uintptr_t)w16_ws) & 15) == 0 && ((uintptr_t)edge_table_ws & 7) == 0,
+                    "posenc_gemm: pe1, w and w16_ws must be 16-byte aligned, edge_table_ws 8-byte aligned");
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.a = pe1; g.r = r; g.k = d; g.lda = d; g.w = w; g.n = d; g.bias = bias; g.c = pe_out; g.ldc = d;
     g.epi = EPI_LIF_ATTN; g.lif = lif4; g.lif_T = lif_steps; g.c2 = attn_in_out;
     g.q = qkv; g.kf = qkv + d; g.ldq = 3 * d; g.tab = (const int2*)edge_table_ws;
     SAPCU_TRY(launch_edge_table(idx, r, m_pts, kk, (int2*)edge_table_ws, (hipStream_t)stream));
-    SAPCU_CHECK_ARG(!split_rows || w16_ws, "posenc_gemm: split rows need the split-f16 kernels (w16_ws)");
     if (w16_ws && (split_rows || d % 64 == 0)) {   // split W into the caller's scratch (hi | lo | counter), then 3 x f16 MFMA
         SAPCU_TRY(split_into_ws(w, (int64_t)d * d, w16_ws, g, (hipStream_t)stream));
         if (split_rows) {     // the production form: pe1 arrives as split rows, attn_in leaves as split rows

@@ -14,6 +14,22 @@
  *   - a handle is immutable after create: concurrent forwards on different streams with
  *     different workspaces are legal.
  *
+ * Memory contract (checked under guard bands by tests/test_gpu_bounds.py; tests/guarded.py):
+ *   - nothing is written outside the declared extents of the outputs and workspaces — not into the columns between `width` and a
+ *     larger pitch (`ld*`), not past the last row, not beyond the bytes a *_workspace_bytes() sizer returned — and nothing read
+ *     outside the declared extents of an input affects a result;
+ *   - workspaces and outputs need NO initialisation by the caller: every counter, key table, cell table and mailbox inside a
+ *     workspace is initialised by the call itself on its stream (the overflow counter of w16_ws, edge_table_ws, the fused
+ *     max-over-points keys and all model scratch, the grid-kNN cell counters, the FPS mailboxes, the training partial sums), so a
+ *     recycled block (torch.empty) is as good as fresh zero pages and results do not depend on what the buffers held.  The ONE
+ *     exception is *gate_open_out of sapcu_neuron_drive, which accumulates and is zeroed by the caller;
+ *   - outputs are written in full over their declared extent (optional outputs: when non-NULL);
+ *   - alignment: a pointer needs the natural alignment of its element type unless its entry point asks for more (the GEMMs:
+ *     A, W and w16_ws 16 bytes).  The vectorised epilogues are chosen per call from the actual alignment of C / bias / lif4 /
+ *     qkv; a less aligned operand takes the element-wise kernel, with the same results bit for bit;
+ *   - "split rows" (sapcu_to_split_rows) own their WHOLE pitch: a split-row tensor of `rows` rows is rows * ld floats, and the
+ *     f16 halves of a row lie anywhere inside its ld floats (so ld >= width, and the last row is a full pitch too).
+ *
  * Each entry point cites the reference lines (relative to /root/reference) it replaces.
  */
 #ifndef SAPCU_H
@@ -73,7 +89,8 @@ int sapcu_displace_f64(const double* queries, const float* normals, const float*
  * sapcu_knn_gather_f64 returns for cloud = pts, queries = pts + 3*row0 with a dist_out (same arithmetic, ascending
  * (distance, index)).  1 <= k <= min(64, n), n <= 2^29.  cell_size: the cell edge, 0 = automatic; any value gives the
  * same result.  Non-finite or |x| > 1e150 coordinates, and n < 4096 with cell_size 0, take the brute-force kernel.
- * The workspace holds sapcu_knn_grid_workspace_bytes(n) bytes.  info_host (HOST int64[4], may be NULL) receives
+ * The workspace holds sapcu_knn_grid_workspace_bytes(n) bytes (uninitialised: the cell counters are zeroed by the call; fewer
+ * bytes -> SAPCU_ERR_ARG, nothing launched), 8-byte aligned (f64 tables inside; else SAPCU_ERR_ARG).  info_host (HOST int64[4], may be NULL) receives
  * {1 = grid used / 0 = brute force, gx, gy, gz}.  Synchronises `stream` once (the grid size is read back).  An empty
  * range (row0 == row1) launches nothing and may pass NULL outputs. */
 int64_t sapcu_knn_grid_workspace_bytes(int64_t n);
@@ -99,7 +116,8 @@ int sapcu_outlier_keep_f64(const double* row_mean, int64_t rows, double mean, do
  * One persistent launch (one workgroup per CU, points and running distances in registers; per step every
  * workgroup publishes its best candidate in a step-tagged mailbox and polls the others' — no atomics, no
  * separate barrier; csrc/fps.hip).  xyz [n,3] f32 device, idx_out [npoint] int64 device; the
- * workspace holds sapcu_fps_workspace_bytes(npoint) bytes.  n <= #CU * 8192 (2,097,152 on MI355X).
+ * workspace holds sapcu_fps_workspace_bytes(npoint) bytes, 8-byte aligned (64-bit mailboxes; else SAPCU_ERR_ARG), uninitialised (the mailboxes are zeroed by the call on
+ * `stream`; fewer bytes -> SAPCU_ERR_WORKSPACE, nothing launched).  n <= #CU * 8192 (2,097,152 on MI355X).
  * Synchronises `stream` before returning (the indices go to the host next, generate.py:74). */
 int64_t sapcu_fps_workspace_bytes(int64_t npoint);
 int sapcu_fps_f32(const float* xyz, int64_t n, int64_t npoint, int64_t* idx_out, void* workspace,
@@ -147,7 +165,8 @@ int sapcu_neuron_drive(const float* x, int64_t rows, int channels, int steps,
  * x, spikes_out, grad_spikes, grad_x: [rows, channels] f32; parameters and their gradients: RAW per-channel values
  * (clamped inside; a parameter outside its clamp range gets zero gradient, as torch.clamp gives it).  1 <= steps <= 8.
  * The backward recomputes the forward from x (nothing is saved between the two calls); parameter gradients are summed
- * over rows in a fixed order (deterministic) through a workspace of sapcu_lif_train_workspace_bytes(rows, channels). */
+ * over rows in a fixed order (deterministic) through a workspace of sapcu_lif_train_workspace_bytes(rows, channels) bytes
+ * (uninitialised; every partial sum is written before it is read).  steps outside 1..8 -> SAPCU_ERR_ARG, nothing launched. */
 int sapcu_lif_train_forward(const float* x, int64_t rows, int channels, int steps, const float* membrane_decay,
                             const float* threshold_adapt, const float* refractory_decay,
                             const float* threshold_base, float* spikes_out, void* stream);
@@ -162,7 +181,9 @@ int sapcu_lif_train_backward(const float* x, const float* grad_spikes, int64_t r
 /* Layer pieces of the training step (row f-4): BatchNorm in TRAINING mode over the rows of a [rows, channels] tensor (what
  * nn.BatchNorm1d/2d do to a 1x1 convolution's output, fn/snn_coder.py:225-252: batch mean and biased variance), its
  * backward, and the weight / bias gradient of the 1x1 convolution.  Deterministic reductions (fixed-order f64 partial
- * sums).  workspace: sapcu_train_workspace_bytes(rows, channels, k) bytes (k = 0 for the BatchNorm calls).
+ * sums).  workspace: sapcu_train_workspace_bytes(rows, channels, k) bytes (k = 0 for the BatchNorm calls), uninitialised;
+ * fewer bytes -> SAPCU_ERR_ARG, nothing launched.  ldy >= n and ldx >= k are row pitches in floats (any value; the gap
+ * columns are neither read into a result nor written); the bias gradient needs ldy == n.
  *   forward : z = (y - mean) * invstd * gamma + beta;   mean/var (biased)/invstd [channels] are outputs (the running
  *             statistics update is the caller's: momentum, unbiased variance)
  *   backward: grad_y = gamma*invstd*(grad_z - mean_r(grad_z) - y_hat*mean_r(grad_z*y_hat)); grad_gamma, grad_beta
@@ -182,7 +203,8 @@ int sapcu_conv1x1_wgrad_f32(const float* grad_y, int ldy, const float* x, int ld
  * (fn/trainer.py:67-83 torch.amp.autocast; BASELINE config 5): operands rounded to bf16 (nearest even), f32 accumulation on the
  * bf16 MFMA; tensors stay f32 in memory.  sapcu_gemm_bf16: c[r,n] = a[r,k] . w[n,k]^T + bias (forward; data gradient with
  * w = W^T); k % 4 == 0.  sapcu_conv1x1_wgrad_bf16: as sapcu_conv1x1_wgrad_f32 (grad_bias summed in f32); workspace
- * sapcu_wgrad_bf16_workspace_bytes(rows, n, k).  Opt-in (sapcu_amd.train.gemm_precision / Trainer(use_amp=True)): this IS a
+ * sapcu_wgrad_bf16_workspace_bytes(rows, n, k) bytes, uninitialised.  sapcu_gemm_bf16: a and w 16-byte aligned, lda % 4 == 0,
+ * lda >= k, ldc >= n (else SAPCU_ERR_ARG).  Opt-in (sapcu_amd.train.gemm_precision / Trainer(use_amp=True)): this IS a
  * precision reduction; the f32 entries above remain the parity reference. */
 int sapcu_gemm_bf16(const float* a, int64_t r, int k, int lda, const float* w, int n, const float* bias, float* c, int ldc,
                     void* stream);
@@ -212,7 +234,9 @@ int sapcu_scatter_add_rows(const float* grad_out, const int64_t* index, int64_t 
  * patch's m points: index[r] / group_src_rows == r / group_rows).  One workgroup per group builds the inverse table in LDS and
  * sums every destination's sources in ascending source order — bit-identical from run to run, which the float-atomic form is
  * not.  This is what the training step uses (index_points' backward, and inside sapcu_softmax_agg_backward for grad_v).
- * bad_count: NULL or a device int that receives the number of entries pointing outside their group (skipped). */
+ * bad_count: NULL or a device int that receives the number of entries pointing outside their group (skipped); the call zeroes
+ * it on `stream` before counting, the caller need not.  ld_src / ld_grad >= d: row pitches in floats; only the first d columns
+ * of a row are read or written. */
 int sapcu_scatter_add_rows_grouped(const float* grad_out, const int64_t* index, int64_t rows, int d, float* grad_src, int ld_grad,
                                    int64_t src_rows, int group_src_rows, int group_rows, int* bad_count, void* stream);
 
@@ -223,7 +247,8 @@ int sapcu_group_max_backward(const float* grad_out, const int32_t* argmax, int64
                              void* stream);
 
 /* In-patch kNN `topk(-|xi|^2 + 2 xi.xj - |xj|^2)` — fn/snn_coder.py:31-39, fd/snn_coder.py:25-32.
- * feat [b, m, ld] f32 (point-major, first c columns used), 1 <= m <= 128, k <= m.
+ * feat [b, m, ld] f32 (point-major, first c columns used, ld >= c any pitch, 4-byte aligned), 1 <= m <= 128, 1 <= k <= m
+ * (else SAPCU_ERR_ARG, nothing launched).
  * idx_out [b,m,k] int32, descending score, equal scores by ascending index. */
 int sapcu_patch_knn(const float* feat, int64_t b, int m, int c, int ld, int k, int32_t* idx_out,
                     void* stream);
@@ -248,7 +273,9 @@ int sapcu_model_create(int kind, const int32_t* hparams_host, int n_hparams, con
                        int64_t blob_floats, const int64_t* dir_host, int n_dir, sapcu_model_t* out);
 int sapcu_model_destroy(sapcu_model_t m);
 
-/* Workspace bytes needed by a forward of b patches of m_pts points. */
+/* Workspace bytes needed by a forward of b patches of m_pts points.  The forwards use no byte beyond it, need no initialisation of
+ * it (every max-over-points key table and counter inside is cleared by the forward itself) and may be handed the same dirty
+ * workspace again.  Tap buffers are written in full over the shapes listed below. */
 int64_t sapcu_workspace_bytes(sapcu_model_t m, int64_t b, int m_pts);
 
 /* Debug taps: `taps` is NULL or a host array of SAPCU_*_TAP_COUNT device pointers (each may be
@@ -317,16 +344,17 @@ int sapcu_model_fused_blocks(sapcu_model_t m, int m_pts, int* mask_host);
 int sapcu_l2_normalize3(const float* in, float* out, int64_t b, void* stream);
 
 /* The library's MFMA GEMMs, exposed for tests and roofline runs:
- *   C[r,n] = epi( A[r,k] * W[n,k]^T + bias[n] ),  k % 32 == 0, A/W 16-byte aligned, lda % 4 == 0.
+ *   C[r,n] = epi( A[r,k] * W[n,k]^T + bias[n] ),  k % 32 == 0, A / W / w16_ws 16-byte aligned, lda % 4 == 0, lda >= k, ldc >= n
+ *   (row pitches in floats; anything else -> SAPCU_ERR_ARG, nothing launched).  C, bias and lif4 need 4-byte alignment only.
  * lif4 == NULL: epi = identity.  Otherwise lif4 = raw neuron parameters [4][n] and the epilogue is
  * the lif_steps-step self-feeding LIF loop (the fused form of conv+BN -> snn loop, fn:317-320).
  * w16_ws == NULL: exact-f32 MFMA kernel.  Otherwise 4*n*k + 16 bytes of scratch: W is split into f16
  * hi/lo halves there and a split-f16 kernel runs (3 x f16 MFMA per product; last 4 bytes of the
- * scratch = count of activation values beyond the f16 range).
+ * scratch = count of activation values beyond the f16 range, ZEROED BY THE CALL: the scratch needs no initialisation).
  * a_split_rows != 0: A is in "split rows" (see sapcu_to_split_rows) -> the all-DMA kernels (lda % 8 == 0): 1 = the kernel
  * the models would pick for the shape (big-tile for >= 1024 rows, else the 128x128 ring kernel), 2 = the ring kernel
  * whatever the shape (the two are bit-identical; the parity tests compare them);
- * c_split_rows: write C as split rows (needs w16_ws). */
+ * c_split_rows: write C as split rows (needs w16_ws): C is then a [r, ldc] container, every row owning its whole pitch. */
 int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, int n, const float* bias,
                    const float* lif4, int lif_steps, float* c, int ldc, void* w16_ws, int a_split_rows,
                    int c_split_rows, void* stream);
@@ -335,14 +363,16 @@ int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, in
  * f16 halves hi = f16_rn(x) and lo = f16_rn(x - hi) inside its row — the operand format of the split-f16 DMA GEMMs.
  * ld_out % 32 == 0: interleaved by groups of 32 elements, group q = one 128-byte line: hi halves of elements
  * 32q..32q+31 at half-index 64q, their lo halves at 64q + 32.  Otherwise: hi at half-index c, lo at ld_out + c.
- * Inside the models the producing kernels write it directly. */
+ * Either way a row's halves lie inside its own ld_out floats and may use any of them: `out` is rows * ld_out floats.
+ * ld_in >= k, ld_out >= k (else SAPCU_ERR_ARG); 4-byte alignment.  Inside the models the producing kernels write it directly. */
 int sapcu_to_split_rows(const float* in, int64_t rows, int k, int ld_in, float* out, int ld_out, void* stream);
 
 /* The positional-encoding GEMM of one fn block — the heaviest single launch shape of the path:
  *   pe[row,:]      = LIF_x4( W . pe1[row,:] + bias )                         (fn/snn_coder.py:360-363)
  *   attn_in[row,:] = q[pt(row),:] - k[nbr(row),:] + pe[row,:]                (fn/snn_coder.py:367-368)
  * pe1 [r,d]; qkv [b*m, 3d] (q | k | v); idx [r] = flattened [b,m,kk] in-patch neighbours; w [d,d];
- * edge_table_ws: 8*r bytes of scratch (row -> (q row, k row) table, rebuilt by every call).
+ * edge_table_ws: exactly 8*r bytes of scratch, 8-byte aligned, uninitialised (row -> (q row, k row) table, rebuilt by every call).
+ * d % 32 == 0; pe1, w and w16_ws 16-byte aligned.  A call outside these returns SAPCU_ERR_ARG before anything is launched.
  * w16_ws: NULL -> exact-f32 MFMA kernel; else 4*d*d + 16 bytes of scratch -> split-f16 (3 x f16 MFMA) kernel.
  * split_rows != 0 (needs w16_ws): pe1 is in split rows and attn_in_out is written as split rows — the form the
  * models' unfused chain runs (all-DMA kernels; 1 = big-tile kernel where it takes the shape, 2 = ring kernel only). */
@@ -363,7 +393,9 @@ int sapcu_posenc_gemm_f32(const float* pe1, int64_t r, int d, const float* w, co
  * [4,d] (membrane_decay, threshold_adapt, refractory_decay, threshold_base; clamped inside as the reference does);
  * res_out [points, d] f32.  Results equal the five-kernel chain (sapcu_posenc_gemm_f32 etc.) bit for bit.
  * workspace: sapcu_fn_edge_chain_workspace_bytes(points, d, kk) bytes (edge records + the split / fragment-ordered weights,
- * rebuilt by every call).  Returns SAPCU_ERR_ARG for any other (d, kk). */
+ * rebuilt by every call; uninitialised, any alignment: the call aligns inside it, and the sizer includes that slack).  A
+ * workspace_bytes below the sizer's value returns SAPCU_ERR_WORKSPACE and any other (d, kk) SAPCU_ERR_ARG, both without
+ * launching anything. */
 int64_t sapcu_fn_edge_chain_workspace_bytes(int64_t points, int d, int kk);
 int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t points, int m_pts, int d, int kk,
                             const float* qkv, const float* w_delta, const float* b_delta, const float* lif_delta,
