@@ -87,6 +87,14 @@ _SIGNATURES = {
 }
 
 EXPORTS = tuple(_SIGNATURES)
+
+# include/sapcu_seeds.h: the device seed flood (additions to the same library; EXPORTS stays "what sapcu.h declares")
+_SEEDS_SIGNATURES = {
+    "sapcu_dense_seeds_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "sapcu_dense_seeds_f64": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64),
+                              c_void_p, c_int64, c_void_p]),
+}
+SEEDS_EXPORTS = tuple(_SEEDS_SIGNATURES)
 _lib = None
 
 
@@ -104,7 +112,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

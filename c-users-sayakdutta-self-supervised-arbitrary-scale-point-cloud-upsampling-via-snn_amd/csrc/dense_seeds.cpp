@@ -284,3 +284,33 @@ extern "C" int sapcu_dense_seeds_host(const double* cloud_host, int64_t n, doubl
     *count_host = count;
     return count <= capacity ? SAPCU_OK : SAPCU_ERR_WORKSPACE;
 }
+
+// ---------------------------------------------------------------------------------- for csrc/dense_seeds_dev.hip
+#include "dense_seeds_host.h"
+
+namespace sapcu_seeds {
+
+struct HostFan {
+    std::vector<P3> pts;
+    KdTree* tree = nullptr;
+    ~HostFan() { delete tree; }
+};
+
+HostFan* host_fan_create(const double* cloud_host, int64_t n) {
+    HostFan* f = new HostFan;
+    f->pts.resize((size_t)n + 1);
+    for (int64_t i = 0; i < n; ++i) f->pts[i] = {{cloud_host[3 * i], cloud_host[3 * i + 1], cloud_host[3 * i + 2]}};
+    f->pts[n] = {{0.0, 0.0, 0.0}};
+    f->tree = new KdTree(f->pts);
+    return f;
+}
+
+double host_fan_distance(const HostFan* f, double cx, double cy, double cz) {
+    return fan_distance(*f->tree, f->pts, P3{{cx, cy, cz}});
+}
+
+void host_fan_destroy(HostFan* f) { delete f; }
+
+double host_six_decimals(double x) { return six_decimals(x); }
+
+}  // namespace sapcu_seeds

@@ -27,65 +27,9 @@
 //     numpy's recursive pairwise sum (split at n/2 rounded down to a multiple of 8, leaves <= 128 as above); the chunk
 //     sums are added in sequence from 0.0 by the caller (sapcu_amd/generation.py), since they may come from several ranks.
 #include "common.h"
+#include "knn_grid.h"
 
 namespace sapcu {
-
-constexpr int KNN_GRID_WAVES = 4;
-constexpr int KNN_GRID_BBOX_BLOCKS = 256;
-constexpr int64_t KNN_GRID_MIN_N = 4096;     // below this (automatic cell size) the brute force costs less than a grid build
-constexpr int SCAN_TILE = 1024;              // 256 threads x 4 counts
-constexpr int STATS_MAX_LEAVES = 512;        // a chunk of <= STATS_MAX_BUFSIZE elements has <= 129 pairwise leaves
-constexpr int64_t STATS_MAX_BUFSIZE = 16384;
-
-struct GridParams {
-    double ox, oy, oz;       // origin = bounding-box minimum
-    double h;                // cell edge
-    double slack;            // absolute margin on the face distances (>> the rounding of keys and faces)
-    int gx, gy, gz;
-    int fallback;            // 1: brute force (non-finite / huge coordinates)
-};
-
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline int64_t grid_cell_cap(int64_t n) { return 2 * n + 64; }
-
-struct GridWs {
-    double* partials;        // [KNN_GRID_BBOX_BLOCKS][8]: min xyz, max xyz, bad flag
-    GridParams* params;
-    int* start;              // [cells + 1]: counts, then exclusive prefix sums
-    int* cursor;             // [cells]
-    int* tile_sums;          // [ceil((cells + 1) / SCAN_TILE)]
-    int* key;                // [n]
-    double* sx;              // [n] each, cell order
-    double* sy;
-    double* sz;
-    int* sidx;               // [n] original index of each sorted point
-    size_t bytes;
-};
-
-static GridWs grid_ws_layout(void* base, int64_t n) {
-    const int64_t cap = grid_cell_cap(n);
-    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
-    char* p = (char*)base;
-    size_t off = 0;
-    GridWs w;
-    auto take = [&](size_t b) {
-        char* r = p ? p + off : nullptr;
-        off += align256(b);
-        return r;
-    };
-    w.partials = (double*)take(sizeof(double) * 8 * KNN_GRID_BBOX_BLOCKS);
-    w.params = (GridParams*)take(sizeof(GridParams));
-    w.start = (int*)take(sizeof(int) * (cap + 1));
-    w.cursor = (int*)take(sizeof(int) * cap);
-    w.tile_sums = (int*)take(sizeof(int) * tiles);
-    w.key = (int*)take(sizeof(int) * n);
-    w.sx = (double*)take(sizeof(double) * n);
-    w.sy = (double*)take(sizeof(double) * n);
-    w.sz = (double*)take(sizeof(double) * n);
-    w.sidx = (int*)take(sizeof(int) * n);
-    w.bytes = off;
-    return w;
-}
 
 // ------------------------------------------------------------------------------------------------------ grid build
 __global__ __launch_bounds__(256) void grid_bbox_kernel(const double* __restrict__ pts, int64_t n, double* __restrict__ partials) {
@@ -178,11 +122,6 @@ __global__ void grid_setup_kernel(const double* __restrict__ partials, int k, in
         p.slack = 1e-11 * (amax + emax + h);
     }
     *prm = p;
-}
-
-__device__ __forceinline__ int grid_coord(double v, double o, double h, int g) {
-    const double t = floor(__ddiv_rn(__dsub_rn(v, o), h));
-    return t < 0.0 ? 0 : (t >= (double)(g - 1) ? g - 1 : (int)t);
 }
 
 __global__ __launch_bounds__(256) void grid_count_kernel(const double* __restrict__ pts, int64_t n, const GridParams* __restrict__ prm,
@@ -380,6 +319,46 @@ __global__ __launch_bounds__(256) void knn_self_grid_kernel(const double* __rest
     }
 }
 
+// exclusive scan of a[0..m) in place; tile_sums: ceil(m / SCAN_TILE) ints of scratch
+int launch_exclusive_scan_int(int* a, int64_t m, int* tile_sums, hipStream_t st) {
+    if (m <= 0) return SAPCU_OK;
+    const int64_t tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
+    hipLaunchKernelGGL(scan_tile_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, a, m, tile_sums);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(256), 0, st, tile_sums, tiles);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, st, a, m, tile_sums);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+// the grid's parameters on the device and in *hp (one stream sync); hp->fallback: nothing else may be built
+int launch_grid_setup(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, GridParams* hp, hipStream_t st) {
+    hipLaunchKernelGGL(grid_bbox_kernel, dim3(KNN_GRID_BBOX_BLOCKS), dim3(256), 0, st, pts, n, w.partials);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, w.partials, k, n, cell_size, grid_cell_cap(n), w.params);
+    SAPCU_CHECK_LAUNCH();
+    SAPCU_CHECK_HIP(hipMemcpyAsync(hp, w.params, sizeof(*hp), hipMemcpyDeviceToHost, st));
+    SAPCU_CHECK_HIP(hipStreamSynchronize(st));
+    return SAPCU_OK;
+}
+
+// counting sort of the points into the cell-ordered copy w.sx|sy|sz|sidx, w.start = first sorted slot of each cell
+int launch_grid_sort(const double* pts, int64_t n, const GridWs& w, const GridParams& hp, hipStream_t st) {
+    const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
+    const int64_t m = cells + 1;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    SAPCU_CHECK_HIP(hipMemsetAsync(w.start, 0, sizeof(int) * m, st));
+    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.params, w.start, w.key);
+    SAPCU_CHECK_LAUNCH();
+    const int rc = launch_exclusive_scan_int(w.start, m, w.tile_sums, st);
+    if (rc != SAPCU_OK) return rc;
+    SAPCU_CHECK_HIP(hipMemcpyAsync(w.cursor, w.start, sizeof(int) * cells, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(grid_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.key, w.cursor, w.sx, w.sy, w.sz, w.sidx);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
 int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row1, int k, double cell_size, int64_t* idx,
                          double* dist, void* ws, int64_t ws_bytes, int64_t* info, hipStream_t st) {
     if (info) info[0] = info[1] = info[2] = info[3] = 0;
@@ -390,13 +369,9 @@ int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row
     GridWs w = grid_ws_layout(ws, n);
     SAPCU_CHECK_ARG(ws && (int64_t)w.bytes <= ws_bytes, "knn_self_grid: workspace of %lld bytes, need %lld",
                     (long long)ws_bytes, (long long)w.bytes);
-    hipLaunchKernelGGL(grid_bbox_kernel, dim3(KNN_GRID_BBOX_BLOCKS), dim3(256), 0, st, pts, n, w.partials);
-    SAPCU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, w.partials, k, n, cell_size, grid_cell_cap(n), w.params);
-    SAPCU_CHECK_LAUNCH();
     GridParams hp;
-    SAPCU_CHECK_HIP(hipMemcpyAsync(&hp, w.params, sizeof(hp), hipMemcpyDeviceToHost, st));
-    SAPCU_CHECK_HIP(hipStreamSynchronize(st));
+    int rc = launch_grid_setup(pts, n, k, cell_size, w, &hp, st);
+    if (rc != SAPCU_OK) return rc;
     if (hp.fallback)
         return launch_knn_outer(pts, n, pts + row0 * 3, rows, k, idx, dist, nullptr, st);
     if (info) {
@@ -405,22 +380,8 @@ int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row
         info[2] = hp.gy;
         info[3] = hp.gz;
     }
-    const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
-    const int64_t m = cells + 1;
-    const int64_t tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    SAPCU_CHECK_HIP(hipMemsetAsync(w.start, 0, sizeof(int) * m, st));
-    hipLaunchKernelGGL(grid_count_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.params, w.start, w.key);
-    SAPCU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_tile_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, w.start, m, w.tile_sums);
-    SAPCU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(256), 0, st, w.tile_sums, tiles);
-    SAPCU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(256), 0, st, w.start, m, w.tile_sums);
-    SAPCU_CHECK_LAUNCH();
-    SAPCU_CHECK_HIP(hipMemcpyAsync(w.cursor, w.start, sizeof(int) * cells, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(grid_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.key, w.cursor, w.sx, w.sy, w.sz, w.sidx);
-    SAPCU_CHECK_LAUNCH();
+    rc = launch_grid_sort(pts, n, w, hp, st);
+    if (rc != SAPCU_OK) return rc;
     const int64_t grid = (rows + KNN_GRID_WAVES - 1) / KNN_GRID_WAVES;
     hipLaunchKernelGGL(knn_self_grid_kernel, dim3((unsigned)grid), dim3(256), 0, st, pts, row0, row1, k, w.params, w.start,
                        w.sx, w.sy, w.sz, w.sidx, idx, dist);

@@ -116,6 +116,8 @@ def upsample_sharded(generator, cloud_dev, seeds_dev, group=None):
 # hold whole chunks of np.mean (generation.outlier_row_align), so that the chunk sums of all ranks, gathered in rank order, are
 # the single-process chunk sums.  Collectives: two broadcasts (seed count, seeds), the refine's all-gather, one all-gather of the
 # chunk sums and one of the keep mask.  gloo moves host tensors, nccl (RCCL) device tensors, as in gather_refined.
+# With generator.seed_source == "device" every rank floods its own copy of the seeds on its GPU (csrc/dense_seeds_dev.hip is
+# deterministic) and the two broadcasts fall away.
 
 def outlier_row_ranges(n, world, kk=None, bufsize=None):
     """[(start, end)] of every rank's rows of the outlier filter over n points: contiguous, in rank order, each start and each
@@ -175,7 +177,10 @@ def upsample_cloud_sharded(generator, data, group=None):
     from . import generation
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     data = np.squeeze(data, 0) if np.ndim(data) == 3 else np.asarray(data)
-    seeds_dev = broadcast_seeds(generator, data, group)
+    if getattr(generator, "seed_source", None) == "device":     # every rank floods its own copy: deterministic, nothing to send
+        seeds_dev = generator._dense_seeds(data)
+    else:
+        seeds_dev = broadcast_seeds(generator, data, group)
     n = seeds_dev.shape[0]
     if n == 0:                              # nothing in the distance band (Generator3D6.upsample_seeds)
         return np.zeros((0, 3), dtype=np.float64)

@@ -56,6 +56,54 @@ def dense_seeds(data, spacing):
         return out[: n.value].copy()
 
 
+def seed_voxel_estimate(n, spacing):
+    """First guess of the voxels a flood meets: a shell of thickness 0.03 + 2 cells (the band reaches 0.015 to either side of the
+    surface and one ring beyond) around a surface of area 6 (a unit-cube-sized shape; a unit sphere has 3.14 and meets 1.76 M voxels
+    at 0.004 against the 3.6 M of this formula).  Only a starting size: dense_seeds_device doubles it when the flood reports more."""
+    cell = float(spacing)
+    return int(min(max(6.0 * (0.03 + 2.0 * cell) / cell ** 3, 1 << 16, 8 * int(n)), 1 << 26))
+
+
+def dense_seeds_device(data, spacing, device, max_voxels=None, capacity=None, stats=None):
+    """``dense_seeds`` on the device (csrc/dense_seeds_dev.hip): the same seeds in the same order with the same 6-decimal values,
+    as a torch f64 [n,3] tensor on ``device``.  ``data``: [N,3] host array or device tensor.  ``max_voxels`` / ``capacity``: starting
+    sizes of the voxel table and the seed buffer (defaults: seed_voxel_estimate, and a quarter of it); both grow on
+    SAPCU_ERR_WORKSPACE and the flood runs again.  ``stats``, a list, receives [levels, voxels evaluated, voxels recomputed on the
+    host, table slots] of the run that succeeded."""
+    import ctypes
+    lib = _lib.load()
+    dev = torch.device(device)
+    if torch.is_tensor(data):
+        cloud = data.to(device=dev, dtype=torch.float64).reshape(-1, 3).contiguous()
+    else:
+        cloud = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64).reshape(-1, 3), device=dev)
+    n = cloud.shape[0]
+    maxv = int(max_voxels) if max_voxels is not None else seed_voxel_estimate(n, spacing)
+    cap = int(capacity) if capacity is not None else max(1 << 16, maxv // 4)
+    while True:
+        nbytes = int(lib.sapcu_dense_seeds_workspace_bytes(n, maxv))
+        if nbytes < 0:
+            raise ValueError("dense_seeds_device: n=%d, max_voxels=%d out of range" % (n, maxv))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+        count = ctypes.c_int64(0)
+        st = (ctypes.c_int64 * 4)()
+        with torch.cuda.device(dev):
+            rc = lib.sapcu_dense_seeds_f64(_lib.ptr(cloud), n, float(spacing), _lib.ptr(out), cap, maxv, ctypes.byref(count), st,
+                                           _lib.ptr(ws), nbytes, _lib.current_stream())
+        if rc == -2:
+            if count.value > cap:          # every seed was counted: the required size
+                cap = int(count.value)
+            else:                          # the voxel table was full
+                maxv *= 2
+            del ws, out
+            continue
+        _lib.check(rc)
+        if stats is not None:
+            stats[:] = list(st)
+        return out[: count.value].clone()
+
+
 def knn_gather(cloud_dev, queries_dev, k, want_dist=False, want_patch=True):
     """Outer kNN on the device: (idx int64 [b,k], dist f64 [b,k] | None, patch f32 [b,k,3] | None)."""
     lib = _lib.load()
@@ -235,12 +283,15 @@ class Generator3D6(object):
 
     # -- seed generation (generation.py:112-118).  Default: in process (csrc/dense_seeds.cpp), identical seeds in
     #    identical order.  seed_source = "subprocess" keeps the reference's mechanics verbatim: os.system("./dense")
-    #    in the working directory, which reads test.xyz and writes target.xyz.
+    #    in the working directory, which reads test.xyz and writes target.xyz.  "device": the same flood on the GPU
+    #    (dense_seeds_device), the seeds stay in HBM and go to the refine as a device tensor.
     seed_source = "inprocess"
 
     def _dense_seeds(self, data):
         if self.seed_source == "inprocess":
             return dense_seeds(data, self.dense_spacing)
+        if self.seed_source == "device":
+            return dense_seeds_device(data, self.dense_spacing, self.device)
         if not os.path.exists("./dense"):
             raise FileNotFoundError("./dense not found in the working directory: the reference shells out to it "
                                     "(generation.py:114-116)")
@@ -336,7 +387,10 @@ class Generator3D6(object):
 
     def upsample_seeds(self, data, seeds, return_unfiltered=False):
         cloud_dev = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64), device=self.device)
-        seeds_dev = torch.as_tensor(np.ascontiguousarray(seeds, dtype=np.float64), device=self.device)
+        if torch.is_tensor(seeds):          # seed_source = "device": already in HBM
+            seeds_dev = seeds.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            seeds_dev = torch.as_tensor(np.ascontiguousarray(seeds, dtype=np.float64), device=self.device)
         if seeds_dev.shape[0] == 0:        # nothing in the distance band (the reference fails inside np.loadtxt here)
             empty = np.zeros((0, 3), dtype=np.float64)
             return (empty, empty) if return_unfiltered else empty

@@ -76,6 +76,13 @@ def main():
           "(%d x %d x %d cells) vs knn_outer brute force %.2f ms (tables equal)" % (
               m, 1e3 * t_host, 1e3 * t_dev, 1e3 * t_grid, info[1], info[2], info[3], 1e3 * t_brute))
 
+    st = []
+    t_sh, s_host = best(lambda: gen.dense_seeds(cloud, 0.004))
+    t_sd, s_dev2 = best(lambda: gen.dense_seeds_device(c_dev, 0.004, dev, stats=st))
+    assert np.array_equal(s_host, s_dev2.cpu().numpy())
+    print("seeds of the N=%d cloud (%d): host %.1f ms (%s threads) | device %.1f ms (arrays equal; %d levels, %d voxels, %d recomputed "
+          "on the host)" % (n, s_host.shape[0], 1e3 * t_sh, os.environ.get("SAPCU_SEED_THREADS", "default"), 1e3 * t_sd, st[0], st[1], st[2]))
+
 
 if __name__ == "__main__":
     main()
