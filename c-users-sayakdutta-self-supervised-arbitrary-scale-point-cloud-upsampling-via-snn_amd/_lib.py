@@ -95,6 +95,11 @@ _SEEDS_SIGNATURES = {
                               c_void_p, c_int64, c_void_p]),
 }
 SEEDS_EXPORTS = tuple(_SEEDS_SIGNATURES)
+
+# test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
+_INTERNAL_SIGNATURES = {
+    "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+}
 _lib = None
 
 
@@ -112,7 +117,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

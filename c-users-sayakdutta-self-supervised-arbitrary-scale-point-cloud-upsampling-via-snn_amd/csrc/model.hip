@@ -95,6 +95,7 @@ struct sapcu_model {
     bool opt_chain;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
     bool opt_chain_wide;       // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
     bool opt_fn_maxfuse;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
+    bool opt_fn_fold_out;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
     bool opt_fd_maxfuse;       // SAPCU_FD_MAXFUSE=0: multi_scale_conv GEMM + rowgroup_max
     bool opt_fd_split;         // SAPCU_FD_SPLIT=0: fd spikes as f32 rows for every step
     bool opt_fd_fused;         // SAPCU_FD_FUSED=0: fd encoder on the per-stage kernels (through HBM) instead of fd_encoder.hip
@@ -105,7 +106,10 @@ struct sapcu_model {
     int64_t fde_off[5];        // offsets (halves) of the five matrices inside fde_w
     float* fde_nprm;
     float* blob;
-    int64_t blob_floats;
+    int64_t blob_floats;       // the caller's blob + (fn) the folded out_proj . fc2 parameters appended at model build
+    // fn: fc2(out_proj(x)) of block l as ONE affine map, W' = W_fc2 . W_out [64, d] and b' = W_fc2 . b_out + b_fc2 [64]: offsets (floats)
+    // into blob, behind the caller's slots, so that the split-f16 planes and the weight range guard cover them like every other slot
+    int64_t fold_w[3], fold_b[3];
     std::vector<int64_t> dir;
     const float* p(int slot) const { return blob + dir[slot]; }
 };
@@ -135,6 +139,26 @@ static bool split_rows_gemm_on_big_tile(const GemmArgs& g, bool allow_bt) { retu
 int launch_gemm_split_rows(const GemmArgs& g, hipStream_t st, bool allow_bt) {
     if (split_rows_gemm_on_big_tile(g, allow_bt)) return launch_gemm_sf16_bt(g, st);
     return launch_gemm_sf16_ring(g, st);
+}
+
+// out_proj followed by fc2 (two affine maps with nothing between them, fn/snn_coder.py:393-394) as one: w_fold [n, d] = w2 . w1 and
+// b_fold [n] = w2 . b1 + b2 for w1 [d, d], b1 [d] (out_proj) and w2 [n, d], b2 [n] (fc2), BatchNorm already folded.  HOST pointers;
+// every sum in f64 over ascending j, rounded to f32 once.  Runs once per model (n d d products).
+static void fold_affine_f64(const float* w1, const float* b1, const float* w2, const float* b2, int d, int n, float* w_fold,
+                            float* b_fold) {
+    std::vector<double> acc((size_t)d);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < d; ++k) acc[k] = 0.0;
+        double bs = 0.0;
+        for (int j = 0; j < d; ++j) {
+            const double a = (double)w2[(int64_t)i * d + j];
+            const float* row = w1 + (int64_t)j * d;
+            for (int k = 0; k < d; ++k) acc[k] += a * (double)row[k];
+            bs += a * (double)b1[j];
+        }
+        for (int k = 0; k < d; ++k) w_fold[(int64_t)i * d + k] = (float)acc[k];
+        b_fold[i] = (float)(bs + (double)b2[i]);
+    }
 }
 
 static bool env_off(const char* name) {
@@ -377,10 +401,16 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
                 }
             }
             // out_proj, fc2 + residual                                              fn:393-394
-            SAPCU_TRY(gemm(m, RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), X, d, EPI_BIAS, st, nullptr, 0, nullptr,
-                           0, SP | (SP << 1)));
-            SAPCU_TRY(gemm(m, X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), cat + 64 * l, 192, EPI_RESID, st,
-                           nullptr, 0, fin, ldin, SP));
+            if (m->opt_fn_fold_out) {
+                // the two layers folded into one at model build (fold_w / fold_b): res goes straight to the block's 64 output columns
+                SAPCU_TRY(gemm(m, RES, P, d, d, m->blob + m->fold_w[l], 64, m->blob + m->fold_b[l], cat + 64 * l, 192, EPI_RESID, st,
+                               nullptr, 0, fin, ldin, SP));
+            } else {
+                SAPCU_TRY(gemm(m, RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), X, d, EPI_BIAS, st, nullptr, 0, nullptr,
+                               0, SP | (SP << 1)));
+                SAPCU_TRY(gemm(m, X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), cat + 64 * l, 192, EPI_RESID, st,
+                               nullptr, 0, fin, ldin, SP));
+            }
             if (taps && taps[SAPCU_FN_TAP_BLOCK1 + l]) {
                 SAPCU_CHECK_HIP(hipMemcpy2DAsync((char*)taps[SAPCU_FN_TAP_BLOCK1 + l] + s * mp * 64 * 4, 64 * 4,
                                                  cat + 64 * l, 192 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
@@ -900,6 +930,8 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
         m->opt_chain_wide = v && strcmp(v, "wide") == 0;
     }
     m->opt_fn_maxfuse = !env_off("SAPCU_FN_MAXFUSE");
+    m->opt_fn_fold_out = !env_off("SAPCU_FN_FOLD_OUT");
+    for (int l = 0; l < 3; ++l) m->fold_w[l] = m->fold_b[l] = 0;
     m->opt_fd_maxfuse = !env_off("SAPCU_FD_MAXFUSE");
     m->opt_fd_split = !env_off("SAPCU_FD_SPLIT");
     m->opt_fd_fused = !env_off("SAPCU_FD_FUSED");
@@ -959,17 +991,50 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
         }
     };
     if (rc == SAPCU_OK) {
-        m->blob_floats = blob_floats;
-        hip_ok(hipMalloc((void**)&m->blob, (size_t)blob_floats * 4), "hipMalloc(blob)");
+        // fn with the fold on: room behind the caller's blob for W' [64, d] | b' [64] of the three blocks (256-byte aligned pieces)
+        int64_t total = blob_floats;
+        if (kind == SAPCU_KIND_FN && m->opt_fn_fold_out) {
+            total = (total + 63) & ~(int64_t)63;
+            for (int l = 0; l < 3; ++l) {
+                m->fold_w[l] = total;
+                total += (int64_t)64 * (128 << l);
+                m->fold_b[l] = total;
+                total += 64;
+            }
+        }
+        m->blob_floats = total;
+        hip_ok(hipMalloc((void**)&m->blob, (size_t)total * 4), "hipMalloc(blob)");
         if (rc == SAPCU_OK) hip_ok(hipMemcpy(m->blob, blob, (size_t)blob_floats * 4, hipMemcpyDeviceToDevice), "copy blob");
+        if (rc == SAPCU_OK && total > blob_floats)
+            hip_ok(hipMemset(m->blob + blob_floats, 0, (size_t)(total - blob_floats) * 4), "memset folded parameters");
+        for (int l = 0; l < 3 && rc == SAPCU_OK && total > blob_floats; ++l) {
+            // W' = W_fc2 . W_out, b' = W_fc2 . b_out + b_fc2 on the host in f64 (once per model), before the split below
+            const int d = 128 << l, sb = FN_BLK0 + l * B_SLOTS;
+            const int64_t need[4] = {(int64_t)d * d, d, (int64_t)64 * d, 64};
+            static const int slot[4] = {B_OUT_W, B_OUT_B, B_FC2_W, B_FC2_B};
+            std::vector<float> h[4], wf((size_t)64 * d), bf(64);
+            for (int q = 0; q < 4 && rc == SAPCU_OK; ++q) {
+                if (m->dir[sb + slot[q]] + need[q] > blob_floats) {
+                    set_error("model_create(fn): slot %d runs past the end of the blob", sb + slot[q]);
+                    rc = SAPCU_ERR_ARG;
+                    break;
+                }
+                h[q].resize((size_t)need[q]);
+                hip_ok(hipMemcpy(h[q].data(), m->p(sb + slot[q]), (size_t)need[q] * 4, hipMemcpyDeviceToHost), "read out_proj / fc2");
+            }
+            if (rc != SAPCU_OK) break;
+            fold_affine_f64(h[0].data(), h[1].data(), h[2].data(), h[3].data(), d, 64, wf.data(), bf.data());
+            hip_ok(hipMemcpy(m->blob + m->fold_w[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice), "copy folded weights");
+            if (rc == SAPCU_OK) hip_ok(hipMemcpy(m->blob + m->fold_b[l], bf.data(), bf.size() * 4, hipMemcpyHostToDevice), "copy folded bias");
+        }
         if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->ovf_dev, 2 * sizeof(int)), "hipMalloc(ovf)");
         if (rc == SAPCU_OK) hip_ok(hipMemset(m->ovf_dev, 0, 2 * sizeof(int)), "memset ovf");
         if (rc == SAPCU_OK && m->sf16) {
-            hip_ok(hipMalloc(&m->w16_hi, (size_t)blob_floats * 2), "hipMalloc(w16_hi)");
-            if (rc == SAPCU_OK) hip_ok(hipMalloc(&m->w16_lo, (size_t)blob_floats * 2), "hipMalloc(w16_lo)");
+            hip_ok(hipMalloc(&m->w16_hi, (size_t)total * 2), "hipMalloc(w16_hi)");
+            if (rc == SAPCU_OK) hip_ok(hipMalloc(&m->w16_lo, (size_t)total * 2), "hipMalloc(w16_lo)");
             if (rc == SAPCU_OK) {
                 int wovf = 0;
-                if (launch_split_weights(m->blob, blob_floats, m->w16_hi, m->w16_lo, m->ovf_dev + 1, nullptr) != SAPCU_OK)
+                if (launch_split_weights(m->blob, total, m->w16_hi, m->w16_lo, m->ovf_dev + 1, nullptr) != SAPCU_OK)
                     rc = SAPCU_ERR_HIP;
                 if (rc == SAPCU_OK) hip_ok(hipMemcpy(&wovf, m->ovf_dev + 1, sizeof(int), hipMemcpyDeviceToHost), "read ovf");
                 if (rc == SAPCU_OK && wovf != 0) m->sf16 = false;   // a parameter exceeds the f16 range: exact-f32 kernels
@@ -1037,6 +1102,15 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
         return rc;
     }
     *out = m;
+    return SAPCU_OK;
+}
+
+// Test hook, not part of include/sapcu.h (HOST pointers, no device work): the routine sapcu_model_create folds out_proj and fc2 of an
+// fn block with — w_out [d, d], b_out [d], w_fc2 [n, d], b_fc2 [n] -> w_fold_out [n, d], b_fold_out [n].
+int sapcu_internal_fold_affine_host(const float* w_out, const float* b_out, const float* w_fc2, const float* b_fc2, int d, int n,
+                                    float* w_fold_out, float* b_fold_out) {
+    SAPCU_CHECK_ARG(w_out && b_out && w_fc2 && b_fc2 && w_fold_out && b_fold_out && d >= 1 && n >= 1, "fold_affine: bad argument");
+    fold_affine_f64(w_out, b_out, w_fc2, b_fc2, d, n, w_fold_out, b_fold_out);
     return SAPCU_OK;
 }
 
