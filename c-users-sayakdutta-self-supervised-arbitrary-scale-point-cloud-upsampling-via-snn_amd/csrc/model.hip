@@ -966,10 +966,19 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
         } else {
             m->k = hp[0]; m->emb = hp[1]; m->T = hp[2]; m->heads = hp[3]; m->nscale = hp[4];
             for (int i = 0; i < m->nscale; ++i) m->ks[i] = hp[5 + i];
-            if (m->k < 1 || m->emb < 32 || m->emb % 32 || m->T < 1 || m->T > 64 || m->heads < 1) {
+            if (m->k < 1 || m->emb < 32 || m->emb % 32 || m->T < 1 || m->T > 64) {
                 set_error("model_create(fd): unsupported hyper-parameters");
                 rc = SAPCU_ERR_ARG;
+            } else if (m->heads < 1 || m->heads > 64 || (m->heads & (m->heads - 1))) {
+                // the decoder's attention splits 64 channels into heads on the lanes of one wave (launch_fd_tail checks it again)
+                set_error("model_create(fd): num_heads must be a power of two <= 64 (got %d)", m->heads);
+                rc = SAPCU_ERR_ARG;
             }
+            for (int i = 0; i < m->nscale && rc == SAPCU_OK; ++i)
+                if (m->ks[i] < 1) {
+                    set_error("model_create(fd): k_scales[%d] = %d, need >= 1", i, m->ks[i]);
+                    rc = SAPCU_ERR_ARG;
+                }
         }
     } else {
         set_error("model_create: unknown kind %d", kind);
@@ -1064,18 +1073,20 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
             if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->gate_dev, sizeof(int)), "hipMalloc(gate)");
             if (rc == SAPCU_OK) hip_ok(hipMemset(m->gate_dev, 0, sizeof(int)), "memset gate");
             // the fused encoder's operands: five matrices in fragment order (hi | lo planes interleaved per fragment), neuron
-            // parameters clamped once
-            if (rc == SAPCU_OK && m->sf16 && m->nscale <= 4 && m->emb >= 96) {
+            // parameters clamped once.  More than four scales: the fused encoder does not take the model, fd_msc_kernel (the x0 path)
+            // does — it reads multi_scale_conv and the neuron parameters only, so the first four matrices stay out (first = 4)
+            if (rc == SAPCU_OK && m->sf16 && m->emb >= 96) {
+                const int first = m->nscale <= 4 ? 0 : 4;
                 const int mats[5][3] = {{FD_FUSE_W, 64, 64 * m->nscale}, {FD_EDGE1_W, 256, 64}, {FD_EDGE2_W, 512, 128},
                                         {FD_EDGE3_W, 1024, 256}, {FD_MSC_W, m->emb, 960}};
                 int64_t halves = 0;
                 for (int i = 0; i < 5; ++i) {
                     m->fde_off[i] = halves;
-                    halves += (int64_t)2 * mats[i][1] * mats[i][2];
+                    if (i >= first) halves += (int64_t)2 * mats[i][1] * mats[i][2];
                 }
                 hip_ok(hipMalloc(&m->fde_w, (size_t)halves * 2), "hipMalloc(fde_w)");
                 if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->fde_nprm, 960 * 8 * sizeof(float)), "hipMalloc(fde_nprm)");
-                for (int i = 0; i < 5 && rc == SAPCU_OK; ++i) {
+                for (int i = first; i < 5 && rc == SAPCU_OK; ++i) {
                     const int64_t wo = m->dir[mats[i][0]];
                     if (launch_pack_frag_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, mats[i][1], mats[i][2],
                                                  (_Float16*)m->fde_w + m->fde_off[i], nullptr) != SAPCU_OK)

@@ -171,6 +171,15 @@ class ImprovedSNNNormalEstimation(_HipModel):
             raise NotImplementedError("use_snn_decoder=True is the reference's legacy decoder (fn/snn_coder.py:481-514); "
                                       "not built")
         self.use_snn_decoder = False
+        # the ranges sapcu_model_create accepts (include/sapcu.h), refused here before any tensor is built
+        if len(k_values) != 3 or any(int(k) < 1 for k in k_values):
+            raise ValueError("k_values must be three neighbour counts >= 1, got %s" % (list(k_values),))
+        if emb_dims < 32 or emb_dims % 32:
+            raise ValueError("emb_dims must be a multiple of 32 (>= 32), got %d" % emb_dims)
+        if time_steps_enc < 1:
+            raise ValueError("time_steps_enc must be >= 1, got %d" % time_steps_enc)
+        if num_heads < 1 or 128 % num_heads:
+            raise ValueError("num_heads must divide 128 (the narrowest block), got %d" % num_heads)
         self.k_values, self.emb_dims, self.time_steps_enc, self.num_heads = list(k_values), emb_dims, time_steps_enc, num_heads
         enc = _Bag()
         enc.conv1 = _conv_bn(3, 64, 1)
@@ -333,6 +342,17 @@ class EnhancedSNNDistanceEstimation(_HipModel):
             raise NotImplementedError("use_snn_decoder=True is the reference's legacy decoder (fd/snn_coder.py:497-664); "
                                       "not built")
         self.use_snn_decoder = False
+        # the ranges sapcu_model_create accepts (include/sapcu.h), refused here before any tensor is built
+        if k < 1:
+            raise ValueError("k must be >= 1, got %d" % k)
+        if emb_dims < 32 or emb_dims % 32:
+            raise ValueError("emb_dims must be a multiple of 32 (>= 32), got %d" % emb_dims)
+        if not 1 <= time_steps_enc <= 64:
+            raise ValueError("time_steps_enc must be in 1..64, got %d" % time_steps_enc)
+        if num_heads < 1 or num_heads > 64 or num_heads & (num_heads - 1):
+            raise ValueError("num_heads must be a power of two <= 64 (the decoder's attention is 64 wide), got %d" % num_heads)
+        if not 1 <= len(k_scales) <= 8 or any(int(ks) < 1 for ks in k_scales):
+            raise ValueError("k_scales must hold 1..8 neighbour counts >= 1, got %s" % (list(k_scales),))
         self.k, self.emb_dims, self.time_steps_enc, self.num_heads, self.k_scales = k, emb_dims, time_steps_enc, num_heads, list(k_scales)
         act = lambda: nn.LeakyReLU(0.2)
         enc = _Bag()

@@ -261,6 +261,13 @@ int sapcu_patch_knn(const float* feat, int64_t b, int m, int c, int ld, int k, i
 /* hparams_host (int32):
  *   fn: [k0, k1, k2, emb_dims, time_steps_enc, num_heads]
  *   fd: [k, emb_dims, time_steps_enc, num_heads, n_scales, ks0, ks1, ...]
+ * Accepted ranges — anything else returns SAPCU_ERR_ARG at create, with *out untouched and sapcu_last_error() set; a handle that
+ * is created computes the reference's function for every patch size 1..128:
+ *   fn: k0, k1, k2 >= 1 (clamped to the patch size per forward, as the reference does); emb_dims a multiple of 32, >= 32;
+ *       time_steps_enc >= 1; num_heads >= 1 dividing 128 (the narrowest block: 1, 2, 4, ..., 128);
+ *   fd: k >= 1 (clamped); emb_dims a multiple of 32, >= 32; time_steps_enc in 1..64; num_heads a power of two <= 64 (the decoder's
+ *       attention is 64 wide; the reference itself takes any divisor of 64, which are the same numbers); n_scales in 1..8; every
+ *       ks_i >= 1 (clamped; in any order).
  * blob: packed f32 parameters on the device (BatchNorm folded, see sapcu_amd/packing.py);
  * dir_host: int64 offsets (in floats) into blob, one per slot of the kind's slot table
  * (SAPCU_FN_SLOTS / SAPCU_FD_SLOTS entries, order fixed by packing.py and model.hip).
@@ -337,6 +344,8 @@ int sapcu_model_gemm_mode(sapcu_model_t m, int* split_f16_host, int* range_overf
  *     per-stage kernels hand the pre-activations x0 to fd_msc_kernel (multi_scale_conv with the spikes of all T steps regenerated
  *     on the CU: larger patches, e.g. the reference's default of 100 points) instead of writing T spike slabs for a GEMM; neither:
  *     the per-stage kernels through HBM.
+ *   By hyper-parameters (default switches, no parameter beyond the f16 range): fn bit l is set iff (d, min(k_l, m_pts)) is exactly
+ *   (128, 24) / (256, 18) / (512, 12); fd is 1 iff m_pts <= 48, n_scales <= 4 and emb_dims >= 96, else 2 iff emb_dims >= 96, else 0.
  * The choice depends on the hyper-parameters, on m_pts and on the switches read at sapcu_model_create (SAPCU_CHAIN=0,
  * SAPCU_FD_FUSED=0, SAPCU_FD_X0=0, SAPCU_GEMM=f32 disable them); it changes speed and workspace size, not results. */
 int sapcu_model_fused_blocks(sapcu_model_t m, int m_pts, int* mask_host);

@@ -37,6 +37,52 @@ def build_gpu_models_under(weights, monkeypatch, env, fn_over=None, fd_over=None
     return out
 
 
+def hparam_row(g, rid):
+    """One row of tests/golden/hparams.npz (`g`: the loaded file): kind 'fn' / 'fd', the constructor override, the oracle's `hp`
+    dict, the patch sizes and the BatchNorm statistics the row carries."""
+    from conftest import FD_KW, FN_KW
+    kind = rid.split("-")[0]
+    over = {}
+    for n in g[rid + "/kw_names"]:
+        v = g["%s/kw:%s" % (rid, n)]
+        over[str(n)] = [int(x) for x in v] if str(n) in ("k_values", "k_scales") else int(v[0])
+    kw = dict(FN_KW if kind == "fn" else FD_KW, **over)
+    names = ("k_values", "emb_dims", "time_steps_enc", "num_heads") if kind == "fn" else ("k", "k_scales", "emb_dims", "time_steps_enc", "num_heads")
+    bn = {str(n): g["%s/bn:%s" % (rid, n)] for n in g[rid + "/bn_names"]}
+    return {"id": rid, "kind": kind, "over": over, "kw": kw, "hp": {n: kw[n] for n in names}, "sizes": [int(m) for m in g[rid + "/sizes"]], "bn": bn}
+
+
+def hparam_model(row):
+    """(module on the CPU, conditioned state dict) for a row of hparams.npz: seed-0 weights, the committed BatchNorm calibration
+    wherever the row's shapes still match it, the row's own statistics on top (make_fixtures.py calibrate_bn_from)."""
+    import sapcu_amd
+    from conftest import golden
+    from sapcu_amd import testing as T
+    cls = sapcu_amd.ImprovedSNNNormalEstimation if row["kind"] == "fn" else sapcu_amd.EnhancedSNNDistanceEstimation
+    model = cls(**row["kw"])
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    bn = {k: v for k, v in dict(golden("bn_calib_%s.npz" % row["kind"])).items() if shapes.get(k) == tuple(v.shape)}
+    bn.update(row["bn"])
+    sd = T.conditioned_state_dict(model.state_dict(), 0, bn_stats=bn)
+    model.load_state_dict(sd, strict=True)
+    return model, sd
+
+
+def build_gpu_hparam_model(row, monkeypatch=None, env=None):
+    """The device model of a row of hparams.npz, its handle created under the environment switches `env` (see
+    build_gpu_models_under)."""
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    model, sd = hparam_model(row)
+    model = model.to(dev())
+    model._engine()
+    for k in (env or {}):
+        monkeypatch.delenv(k, raising=False)
+    if row["kind"] == "fn":
+        model.knn_cache_mode = "fresh"
+    return model, sd
+
+
 def sphere_patches(nq, k, n=5000, qseed=0, skip=0):
     from sapcu_amd import testing as T
     cloud = T.sphere_cloud(n, 0)

@@ -446,10 +446,20 @@ def _models(env_key):
     return _MODELS[env_key]
 
 
-def _fn_case(env_key, b, m, taps):
+def _row_model(rid):
+    """(model, state dict, oracle hp) of a row of tests/golden/hparams.npz — a handle away from the default hyper-parameters, created
+    under the default environment."""
+    if rid not in _MODELS:
+        from conftest import golden
+        row = U.hparam_row(golden("hparams.npz"), rid)
+        _MODELS[rid] = U.build_gpu_hparam_model(row) + (row["hp"],)
+    return _MODELS[rid]
+
+
+def _fn_case(env_key, b, m, taps, row=None):
     def build(A):
         _lib, lib = _lib_()
-        fn, _, sdn, _ = _models(env_key)
+        fn, sdn, hp = _row_model(row) if row else (_models(env_key)[0], _models(env_key)[2], U.FN_HP)
         h = fn._engine()
         patch = U.sphere_patches(b, m, skip=3)
         X = A.inp(patch, offset=4, name="patch")
@@ -475,17 +485,17 @@ def _fn_case(env_key, b, m, taps):
             from oracle import snn_path as O
             assert torch.equal(fn(patch.to(U.dev())).cpu(), o["normals"])           # the module's own call
             with torch.no_grad():
-                n_ref = torch.nn.functional.normalize(O.fn_forward(sdn, patch, U.FN_HP), dim=-1)
+                n_ref = torch.nn.functional.normalize(O.fn_forward(sdn, patch, hp), dim=-1)
             err = (torch.nn.functional.normalize(o["normals"], dim=-1) - n_ref).abs().max().item()
             assert err <= 1e-4, err
         return built(call, outs, ref)
     return build
 
 
-def _fd_case(env_key, b, m, taps):
+def _fd_case(env_key, b, m, taps, row=None):
     def build(A):
         _lib, lib = _lib_()
-        _, fd, _, sdd = _models(env_key)
+        fd, sdd, hp = _row_model(row) if row else (_models(env_key)[1], _models(env_key)[3], U.FD_HP)
         h = fd._engine()
         patch = U.sphere_patches(b, m, skip=5)
         X = A.inp(patch, offset=4, name="patch")
@@ -512,7 +522,7 @@ def _fd_case(env_key, b, m, taps):
             assert torch.equal(fd(patch.to(U.dev())).cpu(), o["dist"])
             knn = o["tap knn"].long()
             with torch.no_grad():
-                d_forced = O.fd_forward(sdd, patch, U.FD_HP, force_idx=[knn[0], knn[1], knn[2]])
+                d_forced = O.fd_forward(sdd, patch, hp, force_idx=[knn[0], knn[1], knn[2]])
             err = (o["dist"] - d_forced).abs().max().item()
             assert err <= 1e-4, err
         return built(call, outs, ref)
@@ -527,6 +537,12 @@ for _env, _b, _m, _taps in (("default", 1, 5, True), ("default", 7, 48, True), (
     case("fn_forward-" + _tag, ["sapcu_fn_forward"], ["sapcu_workspace_bytes"])(_fn_case(_ENVS[_env], _b, _m, _taps))
     case("fd_forward-" + _tag, ["sapcu_fd_forward"], ["sapcu_workspace_bytes"])(_fd_case(_ENVS[_env], _b, _m, _taps))
 
+# handles away from the default hyper-parameters (rows of tests/golden/hparams.npz): the all-unfused fn plan at kk = 20 / 16 and emb 1024,
+# fd with three scales (NS = 3) at k = 20, T = 5, and with five scales (fd_edge0_patch_kernel, the x0 path at 48 points)
+for _row, _b, _m in (("fn-ctor", 3, 48), ("fd-ctor", 3, 48), ("fd-ctor", 2, 100), ("fd-s5", 3, 48)):
+    _kind = _row.split("-")[0]
+    case("%s_forward-%s-b%d-m%d-taps" % (_kind, _row, _b, _m), ["sapcu_%s_forward" % _kind], ["sapcu_workspace_bytes"])(
+        (_fn_case if _kind == "fn" else _fd_case)((), _b, _m, True, row=_row))
 
 # ================================================================================================ in-patch kNN, geometry
 def _patch_knn_case(b, m, c, ld_x, k):

@@ -80,6 +80,37 @@ def test_packer_slot_tables(weights):
     assert d.size == packing.FN_SLOTS == 81 and blob.dtype == np.float32 and (d % 4 == 0).all()
     blob, d = packing.pack_fd(weights("fd"), 4)
     assert d.size == packing.FD_SLOTS == 42 and (d % 4 == 0).all() and d[-1] < blob.size
+    # away from the default configuration (rows of hparams.npz): every slot holds what the state dict says it should, padded to 64 floats
+    import gpu_utils as U
+    g = golden("hparams.npz")
+    up = lambda n: (n + 63) // 64 * 64
+    for rid in ("fn-ctor", "fd-ctor", "fd-s1", "fd-s8"):
+        row = U.hparam_row(g, rid)
+        model, sd = U.hparam_model(row)
+        blob, d = model._pack(sd)
+        kw = row["kw"]
+        assert blob.dtype == np.float32 and (d % 64 == 0).all() and np.isfinite(blob).all()
+        sizes = np.diff(np.append(d, blob.size))
+        if row["kind"] == "fn":
+            emb = kw["emb_dims"]
+            assert d.size == 81
+            want = [64 * 3, 64, 4 * 64]
+            for dm in (128, 256, 512):
+                want += [dm * 64, dm, 4 * dm, 3 * dm * dm, 3 * dm, 4 * 3 * dm]
+                want += [dm * 3, dm, 4 * dm] + 2 * [dm * dm, dm, 4 * dm] + 2 * [dm * dm, dm] + [64 * dm, 64]
+            want += [emb * 192, emb, 4 * emb, 2048 * emb, 2048, 1024 * 2048, 1024, 512 * 1024, 512, 256 * 512, 256, 3 * 256, 3, 3, 3]
+            assert sd["encoder.conv_final.0.weight"].shape == (emb, 192, 1) and sd["encoder.fc_out.weight"].shape == (2048, emb)
+        else:
+            emb, ns, T = kw["emb_dims"], len(kw["k_scales"]), kw["time_steps_enc"]
+            assert d.size == 42
+            want = [ns * 64 * 6, ns * 64, 64 * 64 * ns, 64, 6 * 64]
+            for cin, cout, eif in ((64, 128, 6), (128, 256, 4), (256, 512, 4)):
+                want += [2 * cout * cin, cout, eif * cout]
+            want += [emb * 960, emb, T, 4 * emb, 256 * emb, 256]
+            want += [128 * 256, 128, 128 * 128, 128, 128 * 256, 128, 64 * 128, 64, 64 * 64, 64, 64 * 128, 64]
+            want += [192 * 64, 192, 64 * 64, 64, 64, 64, 64 * 32, 32, 32, 1]
+            assert sd["encoder.scale_fusion.0.weight"].shape == (64, 64 * ns, 1) and sd["encoder.temporal_integration.weights"].shape == (T,)
+        assert [int(x) for x in sizes] == [up(n) for n in want], rid
 
 
 def test_bn_fold_is_exact_in_float64():

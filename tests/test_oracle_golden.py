@@ -1,9 +1,11 @@
 """CPU suite, part 1: the oracle (our restatement) against golden vectors produced by the real
 reference (tests/golden/make_fixtures.py).  This is what pins the oracle."""
 import numpy as np
+import pytest
 import torch
 
 from conftest import FD_KW, FN_KW, golden
+import gpu_utils as U
 from oracle import geom_path as G
 from oracle import snn_path as O
 
@@ -155,6 +157,47 @@ def test_shape_and_T_variants(weights):
                                        g["normals_T%d" % Tv], rtol=0, atol=1e-6)
             np.testing.assert_allclose(O.fd_forward(weights("fd", time_steps_enc=Tv), p, dict(FD_HP, time_steps_enc=Tv)).numpy(),
                                        g["dist_T%d" % Tv], rtol=0, atol=1e-6)
+
+
+@pytest.mark.parametrize("rid", [str(r) for r in golden("hparams.npz")["rows"]])
+def test_hyper_parameter_rows(rid):
+    """hparams.npz: the reference at every hyper-parameter setting of the matrix in make_fixtures.py (constructor defaults, head counts,
+    neighbour counts, scale lists, widths, T = 1), 3 patches per patch size.  The oracle reproduces the normals / distances at the
+    tolerance of variants.npz, picks the reference's xyz neighbour sets (fn) and, under the reference's own feature-space
+    neighbours, its distances (fd).  Well conditioned: f32 and f64 evaluations of the oracle agree to 3e-5.  Not vacuous: outputs differ between the patches, and each of fd's four blocks fires on a
+    fraction of its elements strictly between 0 and 1."""
+    g = golden("hparams.npz")
+    row = U.hparam_row(g, rid)
+    _, sd = U.hparam_model(row)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    for m in row["sizes"]:
+        p = t(g["%s/m%d:patch" % (rid, m)])
+        assert p.shape == (3, m, 3)
+        taps = {}
+        with torch.no_grad():
+            if row["kind"] == "fn":
+                ref = g["%s/m%d:normals" % (rid, m)]
+                out = O.fn_forward(sd, p, row["hp"], taps=taps)
+                out64 = O.fn_forward(sd64, p.double(), row["hp"])
+                for i in range(3):
+                    want = g["%s/m%d:knn%d" % (rid, m, i)].astype(np.int64)
+                    assert want.shape == (3, m, min(row["hp"]["k_values"][i], m))
+                    assert np.array_equal(np.sort(taps["knn_idx"][i].numpy(), -1), want), (m, i)
+                assert ref.std(axis=0).max() > 1e-2, m
+            else:
+                ref = g["%s/m%d:dist" % (rid, m)]
+                force = [t(g["%s/m%d:knn%d" % (rid, m, i)].astype(np.int64)) for i in (1, 2, 3)]
+                assert all(f.shape == (3, m, min(row["hp"]["k"], m)) for f in force)
+                out = O.fd_forward(sd, p, row["hp"], taps=taps, force_idx=force)
+                out64 = O.fd_forward(sd64, p.double(), row["hp"], force_idx=force)
+                assert ref.std() > 1e-2, m
+                for bi in range(4):
+                    fire = float((taps["encoder.spk%d.t0" % bi] > 0.5).float().mean())
+                    assert 0.0 < fire < 1.0, (m, bi, fire)
+        np.testing.assert_allclose(out.numpy(), ref, rtol=0, atol=1e-6, err_msg="%s m=%d" % (rid, m))
+        # well conditioned: the same arithmetic in f64 lands within a third of the GPU tests' 1e-4, so that bar can be asked of an f32
+        # implementation that sums in another order (BatchNorm statistics calibrated on a handful of patches fail this by 100x)
+        assert float((out64 - out.double()).abs().max()) <= 3e-5, (m, float((out64 - out.double()).abs().max()))
 
 
 def test_outer_knn_matches_kdtree_bit_exact():
