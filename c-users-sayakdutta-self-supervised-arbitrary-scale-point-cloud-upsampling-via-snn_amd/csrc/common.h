@@ -65,6 +65,25 @@ inline int device_cu_count() {
     return v;
 }
 
+// Workspace carving (host only).  A workspace has ONE layout function: it carves a WsCarver into a struct of typed pointers and
+// reports bytes().  Called on a null base it is the sizer (every pointer null, same bytes), so the size an entry point promises
+// and the regions it writes cannot disagree.  Regions are rounded up to `granule` bytes (a power of two).
+class WsCarver {
+    char* base_;
+    size_t off_ = 0, granule_;
+public:
+    explicit WsCarver(void* base, size_t granule = 256) : base_((char*)base), granule_(granule) {}
+    template <typename T>
+    T* take(int64_t count) {
+        T* p = base_ ? reinterpret_cast<T*>(base_ + off_) : nullptr;
+        off_ += ((size_t)count * sizeof(T) + granule_ - 1) & ~(granule_ - 1);
+        return p;
+    }
+    size_t bytes() const { return off_; }
+};
+// a caller's workspace pointer moved up to the next 256-byte boundary (null stays null); the sizers add 256 bytes of slack for it
+inline void* ws_align256(void* p) { return (void*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
+
 // ---------------------------------------------------------------------------------------------
 // Neuron arithmetic.  Every product/sum is an explicitly rounded f32 operation in the op order of
 // fn/snn_coder.py:125-146 (ATen evaluates each Python operator as its own rounded kernel), so the

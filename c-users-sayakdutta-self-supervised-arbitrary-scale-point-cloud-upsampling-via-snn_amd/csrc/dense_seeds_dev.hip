@@ -66,32 +66,25 @@ static int64_t seed_slots(int64_t maxv) {
 }
 
 static SeedWs seed_ws_layout(void* base, int64_t n, int64_t maxv) {
-    char* p = (char*)base;
-    size_t off = 0;
+    WsCarver c(base);
     SeedWs w;
-    auto take = [&](size_t b) {
-        char* r = p ? p + off : nullptr;
-        off += align256(b);
-        return r;
-    };
     w.slots = seed_slots(maxv);
     w.nflags = (7 * maxv > n ? 7 * maxv : n) + 1;
-    w.pts = (double*)take(sizeof(double) * 3 * (n + 1));
-    const GridWs g = grid_ws_layout(nullptr, n + 1);
-    w.grid = grid_ws_layout(take(g.bytes), n + 1);
-    w.tab = (double*)take(sizeof(double) * SEED_TAB);
-    w.ctrl = (int*)take(sizeof(int) * C_WORDS);
-    w.ikey = (int*)take(sizeof(int) * n);
-    w.front[0] = (int*)take(sizeof(int) * maxv);
-    w.front[1] = (int*)take(sizeof(int) * maxv);
-    w.best = (double*)take(sizeof(double) * maxv);
-    w.x6 = (double*)take(sizeof(double) * maxv);
-    w.flagged = (int*)take(sizeof(int) * maxv);
-    w.flags = (int*)take(sizeof(int) * w.nflags);
-    w.tile_sums = (int*)take(sizeof(int) * ((w.nflags + SCAN_TILE - 1) / SCAN_TILE));
-    w.tkey = (int*)take(sizeof(int) * w.slots);
-    w.tseq = (int*)take(sizeof(int) * w.slots);
-    w.bytes = off;
+    w.pts = c.take<double>(3 * (n + 1));
+    w.grid = grid_ws_layout(c.take<char>((int64_t)grid_ws_layout(nullptr, n + 1).bytes), n + 1);
+    w.tab = c.take<double>(SEED_TAB);
+    w.ctrl = c.take<int>(C_WORDS);
+    w.ikey = c.take<int>(n);
+    w.front[0] = c.take<int>(maxv);
+    w.front[1] = c.take<int>(maxv);
+    w.best = c.take<double>(maxv);
+    w.x6 = c.take<double>(maxv);
+    w.flagged = c.take<int>(maxv);
+    w.flags = c.take<int>(w.nflags);
+    w.tile_sums = c.take<int>((w.nflags + SCAN_TILE - 1) / SCAN_TILE);
+    w.tkey = c.take<int>(w.slots);
+    w.tseq = c.take<int>(w.slots);
+    w.bytes = c.bytes();
     return w;
 }
 

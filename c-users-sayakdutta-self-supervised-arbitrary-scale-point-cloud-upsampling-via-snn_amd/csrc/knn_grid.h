@@ -20,7 +20,6 @@ struct GridParams {
     int fallback;            // 1: brute force (non-finite / huge coordinates)
 };
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline int64_t grid_cell_cap(int64_t n) { return 2 * n + 64; }
 
 struct GridWs {
@@ -40,25 +39,19 @@ struct GridWs {
 static GridWs grid_ws_layout(void* base, int64_t n) {
     const int64_t cap = grid_cell_cap(n);
     const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
-    char* p = (char*)base;
-    size_t off = 0;
+    WsCarver c(base);
     GridWs w;
-    auto take = [&](size_t b) {
-        char* r = p ? p + off : nullptr;
-        off += align256(b);
-        return r;
-    };
-    w.partials = (double*)take(sizeof(double) * 8 * KNN_GRID_BBOX_BLOCKS);
-    w.params = (GridParams*)take(sizeof(GridParams));
-    w.start = (int*)take(sizeof(int) * (cap + 1));
-    w.cursor = (int*)take(sizeof(int) * cap);
-    w.tile_sums = (int*)take(sizeof(int) * tiles);
-    w.key = (int*)take(sizeof(int) * n);
-    w.sx = (double*)take(sizeof(double) * n);
-    w.sy = (double*)take(sizeof(double) * n);
-    w.sz = (double*)take(sizeof(double) * n);
-    w.sidx = (int*)take(sizeof(int) * n);
-    w.bytes = off;
+    w.partials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
+    w.params = c.take<GridParams>(1);
+    w.start = c.take<int>(cap + 1);
+    w.cursor = c.take<int>(cap);
+    w.tile_sums = c.take<int>(tiles);
+    w.key = c.take<int>(n);
+    w.sx = c.take<double>(n);
+    w.sy = c.take<double>(n);
+    w.sz = c.take<double>(n);
+    w.sidx = c.take<int>(n);
+    w.bytes = c.bytes();
     return w;
 }
 

@@ -1,12 +1,17 @@
 // Model handles and forward orchestration (host code) + the extern "C" ABI of include/sapcu.h.
 //
-// A forward is a fixed sequence of launches on the caller's stream over caller-owned workspace:
-// the 1x1 convolutions / Linears are batched over ALL rows of a chunk of patches and run on the
-// MFMA GEMM (gemm_f32.hip) with the neuron loop fused as its epilogue; the irregular parts
-// (in-patch kNN, gathers, softmax over neighbours, pooling) are the small kernels of
-// patch_ops.hip.  Intermediates of a chunk ([rows, d] f32) live in HBM/Infinity Cache between
-// launches — 288 GB of HBM is what lets [b*m*k, d] tensors exist at all (the reference must keep
-// b <= 400 for them); the chunk size bounds the footprint.
+// A forward is a fixed sequence of launches on the caller's stream over caller-owned workspace, one chunk of patches at a time (the
+// chunk size bounds the footprint: fn_plan / fd_plan).  Each forward has ONE description of its workspace, fn_ws_layout /
+// fd_ws_layout: sapcu_workspace_bytes is that function on a null base, the forward carves the caller's buffer with it.
+//  * In split-f16 mode (the default; SAPCU_GEMM=f32 or a weight outside the f16 range falls back to the exact-f32 MFMA GEMM) the 1x1
+//    convolutions / Linears run as 3 x f16 MFMA GEMMs on weights split once at model build, neuron loops fused as epilogues; tensors
+//    that only feed another GEMM travel as split rows.
+//  * fn: per block fc1 and q|k|v GEMMs over all rows of the chunk, then the edge chain — ONE kernel with the activations in LDS
+//    (fn_edge_chain.hip) for the shapes it takes, else five kernels over [rows * k, d] tensors in HBM — and out_proj . fc2 folded
+//    into one GEMM at model build.
+//  * fd: the encoder as ONE LDS-resident kernel per patch (fd_encoder.hip) up to 48 points; larger patches run the per-stage
+//    front through HBM and multi_scale_conv either from x0 (fd_msc_kernel) or as a GEMM over T spike slabs.
+// The irregular parts (in-patch kNN, gathers, softmax over neighbours, pooling) are the small kernels of patch_ops.hip.
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -71,62 +76,50 @@ static_assert(FD_SLOTS == 42, "fd slot count");
 }  // namespace sapcu
 
 struct sapcu_model {
-    int kind;
+    int kind = 0;
     // fn
-    int kv[3];
+    int kv[3] = {0, 0, 0};
     // fd
-    int k, nscale;
-    int ks[8];
-    int32_t* ks_dev;
-    int* gate_dev;
+    int k = 0, nscale = 0;
+    int ks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int32_t* ks_dev = nullptr;
+    int* gate_dev = nullptr;
     // split-f16 GEMM path: the whole blob pre-split (same indexing), activation-range overflow counter
-    bool sf16;
-    void* w16_hi;
-    void* w16_lo;
-    void* chain_w;             // fn: fc_delta2 | fc_gamma | fc_gamma2 of the three blocks in MFMA-fragment order (fn_edge_chain.hip)
-    int* ovf_dev;
+    bool sf16 = true;
+    void* w16_hi = nullptr;
+    void* w16_lo = nullptr;
+    void* chain_w = nullptr;   // fn: fc_delta2 | fc_gamma | fc_gamma2 of the three blocks in MFMA-fragment order (fn_edge_chain.hip, chain_w_off)
+    int* ovf_dev = nullptr;
     // common
-    int emb, T, heads;
-    int64_t chunk;             // patches per chunk: SAPCU_CHUNK, or 0 = from the workspace budget (ws_budget bytes per forward)
-    int64_t ws_budget;
-    // parity / ablation switches, read from the environment ONCE, at sapcu_model_create (a handle is immutable afterwards: a
-    // forward never calls getenv; tests build a second handle under another environment instead of flipping it mid-process)
-    bool opt_bt;               // SAPCU_BT=0: split-row GEMMs on the ring kernel only
-    bool opt_chain;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
-    bool opt_chain_wide;       // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
-    bool opt_fn_maxfuse;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
-    bool opt_fn_fold_out;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
-    bool opt_fd_maxfuse;       // SAPCU_FD_MAXFUSE=0: multi_scale_conv GEMM + rowgroup_max
-    bool opt_fd_split;         // SAPCU_FD_SPLIT=0: fd spikes as f32 rows for every step
-    bool opt_fd_fused;         // SAPCU_FD_FUSED=0: fd encoder on the per-stage kernels (through HBM) instead of fd_encoder.hip
-    bool opt_fd_x0;            // SAPCU_FD_X0=0: the per-stage path writes T spike slabs for the big-tile GEMM instead of x0 for fd_msc_kernel
+    int emb = 0, T = 0, heads = 0;
+    int64_t chunk = 0;         // patches per chunk: SAPCU_CHUNK, or 0 = from the workspace budget (ws_budget bytes per forward)
+    int64_t ws_budget = 0;
+    // parity / ablation switches, read from the environment ONCE, at sapcu_model_create (read_env_switches; a handle is immutable
+    // afterwards: a forward never calls getenv; tests build a second handle under another environment instead of flipping it mid-process)
+    bool opt_bt = true;               // SAPCU_BT=0: split-row GEMMs on the ring kernel only
+    bool opt_chain = true;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
+    bool opt_chain_wide = false;      // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
+    bool opt_fn_maxfuse = true;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
+    bool opt_fn_fold_out = true;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
+    bool opt_fd_maxfuse = true;       // SAPCU_FD_MAXFUSE=0: multi_scale_conv GEMM + rowgroup_max
+    bool opt_fd_split = true;         // SAPCU_FD_SPLIT=0: fd spikes as f32 rows for every step
+    bool opt_fd_fused = true;         // SAPCU_FD_FUSED=0: fd encoder on the per-stage kernels (through HBM) instead of fd_encoder.hip
+    bool opt_fd_x0 = true;            // SAPCU_FD_X0=0: the per-stage path writes T spike slabs for the big-tile GEMM instead of x0 for fd_msc_kernel
     // fd, fused encoder (fd_encoder.hip): scale_fusion | EdgeConv 1-3 | multi_scale_conv in MFMA-fragment order, clamped neuron
     // parameters of the 960 encoder channels
-    void* fde_w;
-    int64_t fde_off[5];        // offsets (halves) of the five matrices inside fde_w
-    float* fde_nprm;
-    float* blob;
-    int64_t blob_floats;       // the caller's blob + (fn) the folded out_proj . fc2 parameters appended at model build
+    void* fde_w = nullptr;
+    int64_t fde_off[5] = {0, 0, 0, 0, 0};     // offsets (halves) of the five matrices inside fde_w
+    float* fde_nprm = nullptr;
+    float* blob = nullptr;
+    int64_t blob_floats = 0;   // the caller's blob + (fn) the folded out_proj . fc2 parameters appended at model build
     // fn: fc2(out_proj(x)) of block l as ONE affine map, W' = W_fc2 . W_out [64, d] and b' = W_fc2 . b_out + b_fc2 [64]: offsets (floats)
     // into blob, behind the caller's slots, so that the split-f16 planes and the weight range guard cover them like every other slot
-    int64_t fold_w[3], fold_b[3];
+    int64_t fold_w[3] = {0, 0, 0}, fold_b[3] = {0, 0, 0};
     std::vector<int64_t> dir;
     const float* p(int slot) const { return blob + dir[slot]; }
 };
 
 namespace sapcu {
-
-struct Arena {
-    char* base;
-    int64_t cap, off;
-    template <typename T>
-    T* take(int64_t count) {
-        const int64_t bytes = ((count * (int64_t)sizeof(T)) + 255) & ~(int64_t)255;
-        T* p = reinterpret_cast<T*>(base + off);
-        off += bytes;
-        return p;
-    }
-};
 
 static inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
 static inline int imin(int a, int b) { return a < b ? a : b; }
@@ -161,9 +154,40 @@ static void fold_affine_f64(const float* w1, const float* b1, const float* w2, c
     }
 }
 
-static bool env_off(const char* name) {
+static bool env_is(const char* name, const char* value) {
     const char* e = getenv(name);
-    return e && strcmp(e, "0") == 0;
+    return e && strcmp(e, value) == 0;
+}
+
+// the SAPCU_* switches of a handle (include/sapcu.h), read at sapcu_model_create and nowhere else
+static void read_env_switches(sapcu_model* m) {
+    m->sf16 = !env_is("SAPCU_GEMM", "f32");
+    m->opt_bt = !env_is("SAPCU_BT", "0");
+    m->opt_chain = !env_is("SAPCU_CHAIN", "0");
+    m->opt_chain_wide = env_is("SAPCU_CHAIN", "wide");
+    m->opt_fn_maxfuse = !env_is("SAPCU_FN_MAXFUSE", "0");
+    m->opt_fn_fold_out = !env_is("SAPCU_FN_FOLD_OUT", "0");
+    m->opt_fd_maxfuse = !env_is("SAPCU_FD_MAXFUSE", "0");
+    m->opt_fd_split = !env_is("SAPCU_FD_SPLIT", "0");
+    m->opt_fd_fused = !env_is("SAPCU_FD_FUSED", "0");
+    m->opt_fd_x0 = !env_is("SAPCU_FD_X0", "0");
+    const char* ce = getenv("SAPCU_CHUNK");
+    m->chunk = ce ? atoll(ce) : 0;
+    if (m->chunk < 0) m->chunk = 0;
+    // workspace budget per forward (the caller owns the buffer; sapcu_workspace_bytes reports what a batch needs under it):
+    // 20 GiB holds the whole 4096-patch benchmark batch at M = 48 in one chunk (16.9 GB fn, 6.7 GB fd) and cuts the reference's
+    // default M = 100 (8.5 MB per patch) into chunks of ~2400 patches instead of a 35 GB workspace
+    const char* be = getenv("SAPCU_WS_BUDGET_MB");
+    m->ws_budget = (be ? atoll(be) : 20480) * (int64_t)(1 << 20);
+    if (m->ws_budget < (int64_t)(64 << 20)) m->ws_budget = (int64_t)(64 << 20);
+}
+
+// a handle and everything it owns on the device (a failed sapcu_model_create and sapcu_model_destroy)
+static void free_model(sapcu_model* m) {
+    void* const owned[] = {m->w16_hi, m->w16_lo, m->chain_w, m->ovf_dev, m->blob, m->ks_dev, m->gate_dev, m->fde_w, m->fde_nprm};
+    for (void* p : owned)
+        if (p) (void)hipFree(p);
+    delete m;
 }
 
 // Route a GEMM to the split-f16 kernel when the model carries pre-split weights, else to the f32 MFMA kernel.
@@ -212,7 +236,7 @@ static int tap_copy(void* const* taps, int which, int64_t dst_off_bytes, const v
 // ============================================================================ fn
 struct FnPlan {
     int64_t cb;       // patches per chunk
-    int kk[3];
+    int kk[3], kmx;   // neighbours per block (k clamped to the patch), the largest of them
     int64_t edge_floats, edge_floats23;   // per-chunk size of edge buffer 1 (also conv_final's output) and of buffers 2, 3
 };
 
@@ -220,6 +244,13 @@ struct FnPlan {
 // (SAPCU_CHAIN=0 at model creation keeps the five-kernel chain).
 static bool fn_block_fused(const sapcu_model* m, int l, int mp) {
     return m->sf16 && m->chain_w && m->opt_chain && fn_edge_chain_ok(128 << l, imin(m->kv[l], mp));
+}
+
+// the largest neighbour count of the three blocks, each clamped to the patch
+static int fn_kmax(const sapcu_model* m, int mp) {
+    int kmx = 1;
+    for (int l = 0; l < 3; ++l) kmx = kmx > imin(m->kv[l], mp) ? kmx : imin(m->kv[l], mp);
+    return kmx;
 }
 
 // floats of one [rows, d] edge buffer per patch: only the unfused blocks materialise edge tensors; buffer 1 also holds
@@ -235,19 +266,14 @@ static void fn_edge_floats_per_patch(const sapcu_model* m, int mp, int64_t& firs
     }
 }
 
-// bytes of chunk workspace per patch (the footprint is linear in the chunk size): the edge buffers dominate when a block
-// runs unfused
+// bytes of chunk workspace per patch, the budget estimate that picks the chunk size (an input to the layout below, not derived from
+// it: un-rounded, linear in the chunk size): the edge buffers dominate when a block runs unfused
 static int64_t fn_bytes_per_patch(const sapcu_model* m, int mp) {
     int64_t e1, e23;
     fn_edge_floats_per_patch(m, mp, e1, e23);
-    int kmx = 1;
     int64_t idxs = 0;
-    for (int l = 0; l < 3; ++l) {
-        const int kk = imin(m->kv[l], mp);
-        idxs += (int64_t)mp * kk * 4;
-        kmx = kmx > kk ? kmx : kk;
-    }
-    return (e1 + 2 * e23) * 4 + idxs + (int64_t)mp * kmx * 24 + (int64_t)mp * (64 + 192 + 512 + 1536 + 512) * 4 +
+    for (int l = 0; l < 3; ++l) idxs += (int64_t)mp * imin(m->kv[l], mp) * 4;
+    return (e1 + 2 * e23) * 4 + idxs + (int64_t)mp * fn_kmax(m, mp) * 24 + (int64_t)mp * (64 + 192 + 512 + 1536 + 512) * 4 +
            ((int64_t)m->emb + 2048 + 1024 + 512 + 256 + 3) * 4;
 }
 
@@ -266,6 +292,7 @@ static FnPlan fn_plan(const sapcu_model* m, int64_t b, int mp) {
     FnPlan pl;
     pl.cb = chunk_patches(m, b, fn_bytes_per_patch(m, mp));
     for (int l = 0; l < 3; ++l) pl.kk[l] = imin(m->kv[l], mp);
+    pl.kmx = fn_kmax(m, mp);
     int64_t e1, e23;
     fn_edge_floats_per_patch(m, mp, e1, e23);
     pl.edge_floats = e1 * pl.cb;
@@ -273,26 +300,112 @@ static FnPlan fn_plan(const sapcu_model* m, int64_t b, int mp) {
     return pl;
 }
 
-static int64_t fn_ws_bytes(const sapcu_model* m, int64_t b, int mp) {
-    const FnPlan pl = fn_plan(m, b, mp);
+// The chunk workspace of fn_forward, every chunk in the same place.  base = the caller's pointer aligned up to 256 bytes, or null for
+// the size alone (sapcu_workspace_bytes adds the 256 bytes the align-up may cost).
+struct FnWs {
+    int32_t* idx[3];         // [P, kk[l]] in-patch neighbour tables
+    int2* tab;               // [P * kmx] edge table
+    float4* pdiff;           // [P * kmx] position differences
+    float *feat0, *cat, *X, *QKV, *RES;      // [P, 64 | 192 | 512 | 1536 | 512]
+    float* B1;               // edge buffer 1; also conv_final's [P, emb] output, or its max keys [cb, emb] at the head
+    float *B2, *B3;          // edge buffers 2, 3 (unfused blocks only)
+    float *pooled, *enc, *h1, *h2, *h3, *logits;     // [cb, emb | 2048 | 1024 | 512 | 256 | 3]
+    size_t bytes;
+};
+
+static FnWs fn_ws_layout(void* base, const sapcu_model* m, const FnPlan& pl, int mp) {
     const int64_t P = pl.cb * mp;
-    int64_t fl = 0;
-    auto add = [&](int64_t n, int64_t esz) { fl += ((n * esz) + 255) & ~(int64_t)255; };
-    for (int l = 0; l < 3; ++l) add(P * pl.kk[l], 4);          // idx
-    { int kmx = 1; for (int l = 0; l < 3; ++l) kmx = kmx > pl.kk[l] ? kmx : pl.kk[l]; add(P * kmx, 8); add(P * kmx, 16); }   // edge table, position differences
-    add(P * 64, 4); add(P * 192, 4); add(P * 512, 4); add(P * 1536, 4); add(P * 512, 4);
-    add(pl.edge_floats, 4); add(pl.edge_floats23, 4); add(pl.edge_floats23, 4);
-    add(pl.cb * m->emb, 4); add(pl.cb * 2048, 4); add(pl.cb * 1024, 4); add(pl.cb * 512, 4); add(pl.cb * 256, 4);
-    add(pl.cb * 3, 4);
-    return fl + 256;
+    WsCarver c(base);
+    FnWs w;
+    for (int l = 0; l < 3; ++l) w.idx[l] = c.take<int32_t>(P * pl.kk[l]);
+    w.tab = c.take<int2>(P * pl.kmx);
+    w.pdiff = c.take<float4>(P * pl.kmx);
+    w.feat0 = c.take<float>(P * 64);
+    w.cat = c.take<float>(P * 192);
+    w.X = c.take<float>(P * 512);
+    w.QKV = c.take<float>(P * 1536);
+    w.RES = c.take<float>(P * 512);
+    w.B1 = c.take<float>(pl.edge_floats);
+    w.B2 = c.take<float>(pl.edge_floats23);
+    w.B3 = c.take<float>(pl.edge_floats23);
+    w.pooled = c.take<float>(pl.cb * m->emb);
+    w.enc = c.take<float>(pl.cb * 2048);
+    w.h1 = c.take<float>(pl.cb * 1024);
+    w.h2 = c.take<float>(pl.cb * 512);
+    w.h3 = c.take<float>(pl.cb * 256);
+    w.logits = c.take<float>(pl.cb * 3);
+    w.bytes = c.bytes();
+    return w;
+}
+
+// offset (halves) inside chain_w of matrix q (0 fc_delta2, 1 fc_gamma, 2 fc_gamma2) of block l: the blocks in order, each three
+// d x d matrices of hi | lo pairs in MFMA-fragment order; (3, 0) is the size of the whole
+static int64_t chain_w_off(int l, int q) {
+    int64_t off = 0;
+    for (int i = 0; i < l; ++i) off += (int64_t)3 * 2 * (128 << i) * (128 << i);
+    return off + (int64_t)q * 2 * (128 << l) * (128 << l);
+}
+
+// one fn block's edge chain over a chunk of P points: QKV [P, 3d] -> RES [P, d] (SP: as split rows)
+struct FnEdge {
+    const float* pc;         // the chunk's patches
+    int64_t P;
+    int mp, l, d, kk, sb, SP;
+    float sqrt_hd;
+};
+
+// the whole edge chain in one kernel, activations in LDS (fn_edge_chain.hip)      fn:355-389
+static int fn_edge_chain_fused(const sapcu_model* m, const FnWs& W, const FnEdge& e, hipStream_t st) {
+    const int d = e.d, sb = e.sb;
+    ChainArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.P = e.P; ca.m = e.mp; ca.qkv = W.QKV; ca.ldq = 3 * d;
+    ca.wd = m->p(sb + B_DELTA_W); ca.bd = m->p(sb + B_DELTA_B); ca.lifd = m->p(sb + B_DELTA_LIF);
+    const _Float16* cw = (const _Float16*)m->chain_w;
+    ca.w1p = cw + chain_w_off(e.l, 0); ca.b1 = m->p(sb + B_DELTA2_B); ca.lif1 = m->p(sb + B_DELTA2_LIF);
+    ca.w2p = cw + chain_w_off(e.l, 1); ca.b2 = m->p(sb + B_GAMMA_B); ca.lif2 = m->p(sb + B_GAMMA_LIF);
+    ca.w3p = cw + chain_w_off(e.l, 2); ca.b3 = m->p(sb + B_GAMMA2_B);
+    ca.inv_sqrt_hd = 1.0f / e.sqrt_hd;
+    ca.res = W.RES; ca.res_split = e.SP; ca.T = 4; ca.wide_offsets = m->opt_chain_wide ? 1 : 0;
+    return launch_fn_edge_chain(ca, e.pc, W.idx[e.l], d, e.kk, W.tab, W.pdiff, st);
+}
+
+// the same chain as five kernels over [R, d] edge tensors in HBM (R = P * kk rows)
+static int fn_edge_chain_unfused(const sapcu_model* m, const FnWs& W, const FnEdge& e, hipStream_t st) {
+    const int d = e.d, kk = e.kk, sb = e.sb, SP = e.SP;
+    const int64_t R = e.P * kk;
+    const int32_t* idx = W.idx[e.l];
+    // pe1 = LIF(fc_delta(x_i - x_j))                                        fn:310,355-358
+    SAPCU_TRY(launch_fn_pe1(e.pc, idx, R, e.mp, kk, d, m->p(sb + B_DELTA_W), m->p(sb + B_DELTA_B), m->p(sb + B_DELTA_LIF), 4, W.B1, SP,
+                            st));
+    // pe = LIF(fc_delta2(pe1)) -> B2, and in the same epilogue attn_in = q_i - k_j + pe -> B3   fn:360-368
+    {
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.a = W.B1; g.r = R; g.k = d; g.lda = d; g.w = m->p(sb + B_DELTA2_W); g.n = d;
+        g.bias = m->p(sb + B_DELTA2_B); g.c = W.B2; g.ldc = d; g.epi = EPI_LIF_ATTN;
+        g.lif = m->p(sb + B_DELTA2_LIF); g.lif_T = 4; g.c2 = W.B3;
+        g.q = W.QKV; g.kf = W.QKV + d; g.ldq = 3 * d; g.tab = W.tab;
+        g.a_split = SP; g.c2_split = SP;
+        SAPCU_TRY(launch_edge_table(idx, R, e.mp, kk, W.tab, st));
+        SAPCU_TRY(run_gemm(m, g, st));
+    }
+    // g = LIF(fc_gamma(attn_in)) -> B1                                      fn:373-376
+    SAPCU_TRY(gemm(m, W.B3, R, d, d, m->p(sb + B_GAMMA_W), d, m->p(sb + B_GAMMA_B), W.B1, d, EPI_LIF, st, m->p(sb + B_GAMMA_LIF), 4,
+                   nullptr, 0, SP | (SP << 1)));
+    // a = fc_gamma2(g) -> B3                                                fn:378
+    SAPCU_TRY(gemm(m, W.B1, R, d, d, m->p(sb + B_GAMMA2_W), d, m->p(sb + B_GAMMA2_B), W.B3, d, EPI_BIAS, st, nullptr, 0, nullptr, 0, SP));
+    // res = sum_j softmax_j(a / sqrt(hd)) * (v_j + pe)                      fn:379-389
+    return launch_fn_softmax_agg(W.B3, W.B2, W.QKV + 2 * d, 3 * d, idx, e.P, e.mp, kk, d, e.sqrt_hd, W.RES, SP, st);
 }
 
 static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int mp, const int32_t* knn_in,
                       int32_t* knn_out, float* normals, void* ws, int64_t ws_bytes, void* const* taps,
                       hipStream_t st) {
     const FnPlan pl = fn_plan(m, b, mp);
-    if (ws_bytes < fn_ws_bytes(m, b, mp)) {
-        set_error("fn_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)fn_ws_bytes(m, b, mp));
+    const FnWs W = fn_ws_layout(ws_align256(ws), m, pl, mp);
+    if (ws_bytes < (int64_t)W.bytes + 256) {
+        set_error("fn_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)W.bytes + 256);
         return SAPCU_ERR_WORKSPACE;
     }
     // offsets of the three tables inside knn_in / knn_out ([b,m,k0] | [b,m,k1] | [b,m,k2])
@@ -304,118 +417,56 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
     for (int64_t s = 0; s < b; s += pl.cb) {
         const int64_t cb = (b - s) < pl.cb ? (b - s) : pl.cb;
         const int64_t P = cb * mp;
-        Arena A{(char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), ws_bytes, 0};
-        int32_t* idx[3];
-        for (int l = 0; l < 3; ++l) idx[l] = A.take<int32_t>(pl.cb * mp * pl.kk[l]);
-        int kmx = 1;
-        for (int l = 0; l < 3; ++l) kmx = kmx > pl.kk[l] ? kmx : pl.kk[l];
-        int2* tab = A.take<int2>(pl.cb * mp * kmx);
-        float4* pdiff = A.take<float4>(pl.cb * mp * kmx);
-        float* feat0 = A.take<float>(pl.cb * mp * 64);
-        float* cat = A.take<float>(pl.cb * mp * 192);
-        float* X = A.take<float>(pl.cb * mp * 512);
-        float* QKV = A.take<float>(pl.cb * mp * 1536);
-        float* RES = A.take<float>(pl.cb * mp * 512);
-        float* B1 = A.take<float>(pl.edge_floats);
-        float* B2 = A.take<float>(pl.edge_floats23);
-        float* B3 = A.take<float>(pl.edge_floats23);
-        float* pooled = A.take<float>(pl.cb * m->emb);
-        float* enc = A.take<float>(pl.cb * 2048);
-        float* h1 = A.take<float>(pl.cb * 1024);
-        float* h2 = A.take<float>(pl.cb * 512);
-        float* h3 = A.take<float>(pl.cb * 256);
-        float* logits = A.take<float>(pl.cb * 3);
         const float* pc = patch + s * mp * 3;
 
         // in-patch neighbour tables: replayed (reference KNNCache) or computed from this chunk (one xyz
         // ranking per patch serves the three blocks' k values)
-        if (!knn_in) SAPCU_TRY(launch_patch_knn_multi(pc, cb, (int64_t)mp * 3, mp, 3, 3, 3, pl.kk, idx, st));
+        if (!knn_in) SAPCU_TRY(launch_patch_knn_multi(pc, cb, (int64_t)mp * 3, mp, 3, 3, 3, pl.kk, W.idx, st));
         for (int l = 0; l < 3; ++l) {
             const int64_t cnt = P * pl.kk[l];
             if (knn_in)
-                SAPCU_CHECK_HIP(hipMemcpyAsync(idx[l], knn_in + tab_off[l] + s * mp * pl.kk[l], cnt * 4,
+                SAPCU_CHECK_HIP(hipMemcpyAsync(W.idx[l], knn_in + tab_off[l] + s * mp * pl.kk[l], cnt * 4,
                                                hipMemcpyDeviceToDevice, st));
             if (knn_out)
-                SAPCU_CHECK_HIP(hipMemcpyAsync(knn_out + tab_off[l] + s * mp * pl.kk[l], idx[l], cnt * 4,
+                SAPCU_CHECK_HIP(hipMemcpyAsync(knn_out + tab_off[l] + s * mp * pl.kk[l], W.idx[l], cnt * 4,
                                                hipMemcpyDeviceToDevice, st));
         }
-        SAPCU_TRY(launch_fn_stem(pc, P, m->p(FN_STEM_W), m->p(FN_STEM_B), m->p(FN_STEM_LIF), m->T, feat0, st));
-        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_STEM, s * mp * 64 * 4, feat0, P * 64 * 4, st));
+        SAPCU_TRY(launch_fn_stem(pc, P, m->p(FN_STEM_W), m->p(FN_STEM_B), m->p(FN_STEM_LIF), m->T, W.feat0, st));
+        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_STEM, s * mp * 64 * 4, W.feat0, P * 64 * 4, st));
 
-        const float* fin = feat0;
+        const float* fin = W.feat0;
         int ldin = 64;
         for (int l = 0; l < 3; ++l) {
             const int d = 128 << l;
-            const int kk = pl.kk[l];
-            const int64_t R = P * kk;
             const int sb = FN_BLK0 + l * B_SLOTS;
             // Tensors that only feed another GEMM travel as split rows (SP) in split-f16 mode: their producer
             // writes f16 hi/lo halves and the consuming GEMM streams them by LDS-DMA (gemm_sf16_ring.hip).
             const int SP = m->sf16 ? 1 : 0;
+            float* const out = W.cat + 64 * l;             // the block's 64 output columns
             // x = LIF(fc1(feat))                                                    fn:317-320
-            SAPCU_TRY(gemm(m, fin, P, 64, ldin, m->p(sb + B_FC1_W), d, m->p(sb + B_FC1_B), X, d, EPI_LIF, st,
+            SAPCU_TRY(gemm(m, fin, P, 64, ldin, m->p(sb + B_FC1_W), d, m->p(sb + B_FC1_B), W.X, d, EPI_LIF, st,
                            m->p(sb + B_SNN1), 4, nullptr, 0, SP << 1));
             // q|k|v = LIF(w_qs|w_ks|w_vs (x))                                       fn:322-335
-            SAPCU_TRY(gemm(m, X, P, d, d, m->p(sb + B_QKV_W), 3 * d, m->p(sb + B_QKV_B), QKV, 3 * d, EPI_LIF, st,
+            SAPCU_TRY(gemm(m, W.X, P, d, d, m->p(sb + B_QKV_W), 3 * d, m->p(sb + B_QKV_B), W.QKV, 3 * d, EPI_LIF, st,
                            m->p(sb + B_QKV_LIF), 4, nullptr, 0, SP));
-            const float sqrt_hd = (float)sqrt((double)(d / m->heads));
-            if (fn_block_fused(m, l, mp)) {
-                // the whole edge chain in one kernel, activations in LDS (fn_edge_chain.hip)      fn:355-389
-                ChainArgs ca;
-                memset(&ca, 0, sizeof(ca));
-                ca.P = P; ca.m = mp; ca.qkv = QKV; ca.ldq = 3 * d;
-                ca.wd = m->p(sb + B_DELTA_W); ca.bd = m->p(sb + B_DELTA_B); ca.lifd = m->p(sb + B_DELTA_LIF);
-                static const int64_t cw_off[3] = {0, (int64_t)3 * 2 * 128 * 128, (int64_t)3 * 2 * (128 * 128 + 256 * 256)};
-                const _Float16* cw = (const _Float16*)m->chain_w + cw_off[l];
-                ca.w1p = cw; ca.b1 = m->p(sb + B_DELTA2_B); ca.lif1 = m->p(sb + B_DELTA2_LIF);
-                ca.w2p = cw + (int64_t)d * d * 2; ca.b2 = m->p(sb + B_GAMMA_B); ca.lif2 = m->p(sb + B_GAMMA_LIF);
-                ca.w3p = cw + (int64_t)2 * d * d * 2; ca.b3 = m->p(sb + B_GAMMA2_B);
-                ca.inv_sqrt_hd = 1.0f / sqrt_hd;
-                ca.res = RES; ca.res_split = SP; ca.T = 4; ca.wide_offsets = m->opt_chain_wide ? 1 : 0;
-                SAPCU_TRY(launch_fn_edge_chain(ca, pc, idx[l], d, kk, tab, pdiff, st));
-            } else {
-                // pe1 = LIF(fc_delta(x_i - x_j))                                        fn:310,355-358
-                SAPCU_TRY(launch_fn_pe1(pc, idx[l], R, mp, kk, d, m->p(sb + B_DELTA_W), m->p(sb + B_DELTA_B),
-                                        m->p(sb + B_DELTA_LIF), 4, B1, SP, st));
-                // pe = LIF(fc_delta2(pe1)) -> B2, and in the same epilogue attn_in = q_i - k_j + pe -> B3   fn:360-368
-                {
-                    GemmArgs g;
-                    memset(&g, 0, sizeof(g));
-                    g.a = B1; g.r = R; g.k = d; g.lda = d; g.w = m->p(sb + B_DELTA2_W); g.n = d;
-                    g.bias = m->p(sb + B_DELTA2_B); g.c = B2; g.ldc = d; g.epi = EPI_LIF_ATTN;
-                    g.lif = m->p(sb + B_DELTA2_LIF); g.lif_T = 4; g.c2 = B3;
-                    g.q = QKV; g.kf = QKV + d; g.ldq = 3 * d; g.tab = tab;
-                    g.a_split = SP; g.c2_split = SP;
-                    SAPCU_TRY(launch_edge_table(idx[l], R, mp, kk, tab, st));
-                    SAPCU_TRY(run_gemm(m, g, st));
-                }
-                // g = LIF(fc_gamma(attn_in)) -> B1                                      fn:373-376
-                SAPCU_TRY(gemm(m, B3, R, d, d, m->p(sb + B_GAMMA_W), d, m->p(sb + B_GAMMA_B), B1, d, EPI_LIF, st,
-                               m->p(sb + B_GAMMA_LIF), 4, nullptr, 0, SP | (SP << 1)));
-                {
-                    // a = fc_gamma2(g) -> B3                                            fn:378
-                    SAPCU_TRY(gemm(m, B1, R, d, d, m->p(sb + B_GAMMA2_W), d, m->p(sb + B_GAMMA2_B), B3, d, EPI_BIAS, st, nullptr, 0,
-                                   nullptr, 0, SP));
-                    // res = sum_j softmax_j(a / sqrt(hd)) * (v_j + pe)                  fn:379-389
-                    SAPCU_TRY(launch_fn_softmax_agg(B3, B2, QKV + 2 * d, 3 * d, idx[l], P, mp, kk, d, sqrt_hd, RES, SP, st));
-                }
-            }
+            const FnEdge e{pc, P, mp, l, d, pl.kk[l], sb, SP, (float)sqrt((double)(d / m->heads))};
+            SAPCU_TRY(fn_block_fused(m, l, mp) ? fn_edge_chain_fused(m, W, e, st) : fn_edge_chain_unfused(m, W, e, st));
             // out_proj, fc2 + residual                                              fn:393-394
             if (m->opt_fn_fold_out) {
                 // the two layers folded into one at model build (fold_w / fold_b): res goes straight to the block's 64 output columns
-                SAPCU_TRY(gemm(m, RES, P, d, d, m->blob + m->fold_w[l], 64, m->blob + m->fold_b[l], cat + 64 * l, 192, EPI_RESID, st,
+                SAPCU_TRY(gemm(m, W.RES, P, d, d, m->blob + m->fold_w[l], 64, m->blob + m->fold_b[l], out, 192, EPI_RESID, st,
                                nullptr, 0, fin, ldin, SP));
             } else {
-                SAPCU_TRY(gemm(m, RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), X, d, EPI_BIAS, st, nullptr, 0, nullptr,
+                SAPCU_TRY(gemm(m, W.RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), W.X, d, EPI_BIAS, st, nullptr, 0, nullptr,
                                0, SP | (SP << 1)));
-                SAPCU_TRY(gemm(m, X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), cat + 64 * l, 192, EPI_RESID, st,
+                SAPCU_TRY(gemm(m, W.X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), out, 192, EPI_RESID, st,
                                nullptr, 0, fin, ldin, SP));
             }
             if (taps && taps[SAPCU_FN_TAP_BLOCK1 + l]) {
                 SAPCU_CHECK_HIP(hipMemcpy2DAsync((char*)taps[SAPCU_FN_TAP_BLOCK1 + l] + s * mp * 64 * 4, 64 * 4,
-                                                 cat + 64 * l, 192 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
+                                                 out, 192 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
             }
-            fin = cat + 64 * l;
+            fin = out;
             ldin = 192;
         }
         // conv_final + LIF x T_enc, max over points, fc_out                          fn:465-475
@@ -424,27 +475,27 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
             // multi_scale_conv): the [P, emb] activation is never written.  Keys live at the head of the unused B1 area.
             GemmArgs g;
             memset(&g, 0, sizeof(g));
-            g.a = cat; g.r = P; g.k = 192; g.lda = 192; g.w = m->p(FN_FINAL_W); g.n = m->emb; g.bias = m->p(FN_FINAL_B);
+            g.a = W.cat; g.r = P; g.k = 192; g.lda = 192; g.w = m->p(FN_FINAL_W); g.n = m->emb; g.bias = m->p(FN_FINAL_B);
             g.ldc = m->emb; g.epi = EPI_LIF_MAX; g.lif = m->p(FN_FINAL_LIF); g.lif_T = m->T;
-            g.max_keys = reinterpret_cast<unsigned*>(B1); g.max_m = mp;
+            g.max_keys = reinterpret_cast<unsigned*>(W.B1); g.max_m = mp;
             SAPCU_CHECK_HIP(hipMemsetAsync(g.max_keys, 0, (size_t)cb * m->emb * 4, st));
             SAPCU_TRY(run_gemm(m, g, st));
-            SAPCU_TRY(launch_decode_max_keys(g.max_keys, cb * m->emb, pooled, st));
+            SAPCU_TRY(launch_decode_max_keys(g.max_keys, cb * m->emb, W.pooled, st));
         } else {
-            SAPCU_TRY(gemm(m, cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), B1, m->emb, EPI_LIF, st,
+            SAPCU_TRY(gemm(m, W.cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), W.B1, m->emb, EPI_LIF, st,
                            m->p(FN_FINAL_LIF), m->T));
-            SAPCU_TRY(launch_rowgroup_max(B1, cb, mp, m->emb, pooled, st));
+            SAPCU_TRY(launch_rowgroup_max(W.B1, cb, mp, m->emb, W.pooled, st));
         }
-        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_POOLED, s * m->emb * 4, pooled, cb * m->emb * 4, st));
-        SAPCU_TRY(gemm(m, pooled, cb, m->emb, m->emb, m->p(FN_FCOUT_W), 2048, m->p(FN_FCOUT_B), enc, 2048, EPI_BIAS, st));
-        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_ENC, s * 2048 * 4, enc, cb * 2048 * 4, st));
+        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_POOLED, s * m->emb * 4, W.pooled, cb * m->emb * 4, st));
+        SAPCU_TRY(gemm(m, W.pooled, cb, m->emb, m->emb, m->p(FN_FCOUT_W), 2048, m->p(FN_FCOUT_B), W.enc, 2048, EPI_BIAS, st));
+        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_ENC, s * 2048 * 4, W.enc, cb * 2048 * 4, st));
         // decoder MLP (Linear+BN+GELU) x3, Linear(256,3), LayerNorm(3), normalize    fn:542-549
-        SAPCU_TRY(gemm(m, enc, cb, 2048, 2048, m->p(FN_MLP0_W), 1024, m->p(FN_MLP0_B), h1, 1024, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, h1, cb, 1024, 1024, m->p(FN_MLP1_W), 512, m->p(FN_MLP1_B), h2, 512, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, h2, cb, 512, 512, m->p(FN_MLP2_W), 256, m->p(FN_MLP2_B), h3, 256, EPI_GELU, st));
-        SAPCU_TRY(launch_fn_tail(h3, cb, 256, m->p(FN_HEAD_W), m->p(FN_HEAD_B), m->p(FN_LN_W), m->p(FN_LN_B), logits,
+        SAPCU_TRY(gemm(m, W.enc, cb, 2048, 2048, m->p(FN_MLP0_W), 1024, m->p(FN_MLP0_B), W.h1, 1024, EPI_GELU, st));
+        SAPCU_TRY(gemm(m, W.h1, cb, 1024, 1024, m->p(FN_MLP1_W), 512, m->p(FN_MLP1_B), W.h2, 512, EPI_GELU, st));
+        SAPCU_TRY(gemm(m, W.h2, cb, 512, 512, m->p(FN_MLP2_W), 256, m->p(FN_MLP2_B), W.h3, 256, EPI_GELU, st));
+        SAPCU_TRY(launch_fn_tail(W.h3, cb, 256, m->p(FN_HEAD_W), m->p(FN_HEAD_B), m->p(FN_LN_W), m->p(FN_LN_B), W.logits,
                                  normals + s * 3, st));
-        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_LOGITS, s * 3 * 4, logits, cb * 3 * 4, st));
+        SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_LOGITS, s * 3 * 4, W.logits, cb * 3 * 4, st));
     }
     return SAPCU_OK;
 }
@@ -452,7 +503,7 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
 // ============================================================================ fd
 struct FdPlan {
     int64_t cb;
-    int kmax0, kk;
+    int kmax0, kk;             // largest scale k and the feature-space k, both clamped to the patch
     bool fused;                // the whole encoder in fd_encoder.hip: no per-point intermediates in the workspace
     bool x0path;               // per-stage front + fd_msc_kernel: x0 [P, 960] and ONE spike slab instead of T slabs (round 4)
     bool maxfuse;              // multi_scale_conv's max over points inside the GEMM: the [T*P, emb] aggregate is never written
@@ -471,224 +522,265 @@ static bool fd_x0_path(const sapcu_model* m, int mp) {
            m->fde_nprm && fd_msc_ok(mp, m->emb, m->T);
 }
 
+// the largest k over the scales, clamped to the patch (every scale's table is a prefix of the sorted top-kmax0 list)
+static int fd_kmax0(const sapcu_model* m, int mp) {
+    int kmax = 1;
+    for (int i = 0; i < m->nscale; ++i) kmax = kmax > m->ks[i] ? kmax : m->ks[i];
+    return imin(kmax, mp);
+}
+
 static FdPlan fd_plan(const sapcu_model* m, int64_t b, int mp) {
     FdPlan pl;
     pl.fused = fd_encoder_fused(m, mp);
     pl.x0path = fd_x0_path(m, mp);
     pl.maxfuse = m->sf16 && m->opt_fd_maxfuse;
-    if (pl.fused) {
-        // the encoder's intermediates never leave the CU: per patch only pooled [T, emb], the encoding and the decoder's rows
-        const int64_t per_patch_f = ((int64_t)(m->T + 1) * m->emb + 256 + 3 * 128 + 3 * 64 + 192 + 64) * 4;
-        pl.cb = chunk_patches(m, b, per_patch_f);
-        int kmaxf = 1;
-        for (int i = 0; i < m->nscale; ++i) kmaxf = kmaxf > m->ks[i] ? kmaxf : m->ks[i];
-        pl.kmax0 = imin(kmaxf, mp);
-        pl.kk = imin(m->k, mp);
-        return pl;
-    }
-    // fd intermediates: T x 960 spikes (+ the T x emb aggregate per point only when the max is NOT taken inside the GEMM) + 960 +
-    // 1024 + block-0 features per point, neighbour tables
-    int kmax0 = 1;
-    for (int i = 0; i < m->nscale; ++i) kmax0 = kmax0 > m->ks[i] ? kmax0 : m->ks[i];
-    const int64_t slabs = pl.x0path ? 2 : m->T;        // x0 path: the step-0 spike slab (split rows) + x0, whatever T
-    const int64_t per_patch = (int64_t)mp * ((slabs * 960 + 960 + 1024 + 64 * (m->nscale + 1)) * 4 +
-                                            (int64_t)(imin(kmax0, mp) + 3 * imin(m->k, mp)) * 4) +
-                              (int64_t)m->T * pl.agg_rows(mp) * m->emb * 4 +
-                              ((int64_t)(m->T + 1) * m->emb + 256 + 3 * 128 + 3 * 64 + 192 + 64) * 4;
-    pl.cb = chunk_patches(m, b, per_patch);
-    int kmax = 1;
-    for (int i = 0; i < m->nscale; ++i) kmax = kmax > m->ks[i] ? kmax : m->ks[i];
-    pl.kmax0 = imin(kmax, mp);
+    pl.kmax0 = fd_kmax0(m, mp);
     pl.kk = imin(m->k, mp);
+    // bytes per patch, the budget estimate that picks the chunk size (an input to the layout below, not derived from it).  With the
+    // fused encoder the intermediates never leave the CU: per patch only pooled [T, emb], the encoding and the decoder's rows
+    int64_t per_patch = ((int64_t)(m->T + 1) * m->emb + 256 + 3 * 128 + 3 * 64 + 192 + 64) * 4;
+    if (!pl.fused) {
+        // per-stage intermediates: T x 960 spikes (+ the T x emb aggregate per point only when the max is NOT taken inside the GEMM) +
+        // 960 + 1024 + block-0 features per point, neighbour tables
+        const int64_t slabs = pl.x0path ? 2 : m->T;        // x0 path: the step-0 spike slab (split rows) + x0, whatever T
+        per_patch = (int64_t)mp * ((slabs * 960 + 960 + 1024 + 64 * (m->nscale + 1)) * 4 + (int64_t)(pl.kmax0 + 3 * pl.kk) * 4) +
+                    (int64_t)m->T * pl.agg_rows(mp) * m->emb * 4 + per_patch;
+    }
+    pl.cb = chunk_patches(m, b, per_patch);
     return pl;
 }
 
-static int64_t fd_ws_bytes(const sapcu_model* m, int64_t b, int mp) {
-    const FdPlan pl = fd_plan(m, b, mp);
-    const int64_t P = pl.cb * mp;
-    int64_t fl = 0;
-    auto add = [&](int64_t n, int64_t esz) { fl += ((n * esz) + 255) & ~(int64_t)255; };
-    if (!pl.fused) {
-        add(P * pl.kmax0, 4); add(3 * P * pl.kk, 4);
-        add(P * 64 * m->nscale, 4); add(P * 64, 4);
-        add((pl.x0path ? 1 : (int64_t)m->T) * P * 960, 4); add(P * 960, 4); add(P * 1024, 4); add((int64_t)m->T * pl.cb * pl.agg_rows(mp) * m->emb, 4);
-        if (pl.x0path) add(P * 960, 4);
+// The chunk workspace of fd_forward, every chunk in the same place; base as for fn_ws_layout.  The per-point intermediates exist
+// only on the per-stage path (pp: the fused encoder keeps them on the CU and their regions are empty).
+struct FdWs {
+    int32_t* idx0;           // [P, kmax0] xyz neighbours
+    int32_t* idxb;           // [3][P, kk] feature-space neighbours of blocks 1..3
+    float* E0;               // [P, 64 * nscale]
+    float* FUSED;            // [P, 64]
+    float* SPK;              // [T][P, 960] spikes (x0 path: one slab), f32 or split rows
+    float* F0;               // [P, 960] step-0 spikes as f32 when SPK holds split rows
+    float* AB;               // [P, 1024] factored EdgeConv products
+    float* AGG;              // [T * P, emb] aggregate; maxfuse: the [T, cb, emb] max keys only
+    float* X0;               // x0 path: [P, 960] pre-activations
+    float *POOLED, *ENC;     // [T, cb, emb], [cb, emb]
+    float *D1, *D2a, *D2b, *D2c, *D3a, *D3b, *D3c, *QKV, *ATT;      // decoder rows [cb, 256 | 128 x 3 | 64 x 3 | 192 | 64]
+    size_t bytes;
+};
+
+static FdWs fd_ws_layout(void* base, const sapcu_model* m, const FdPlan& pl, int mp) {
+    const int64_t cb = pl.cb, T = m->T, emb = m->emb;
+    const int64_t P = pl.fused ? 0 : cb * mp;
+    WsCarver c(base);
+    FdWs w;
+    w.idx0 = c.take<int32_t>(P * pl.kmax0);
+    w.idxb = c.take<int32_t>(3 * P * pl.kk);
+    w.E0 = c.take<float>(P * 64 * m->nscale);
+    w.FUSED = c.take<float>(P * 64);
+    w.SPK = c.take<float>((pl.x0path ? 1 : T) * P * 960);
+    w.F0 = c.take<float>(P * 960);
+    w.AB = c.take<float>(P * 1024);
+    w.AGG = c.take<float>(pl.fused ? 0 : T * cb * pl.agg_rows(mp) * emb);
+    w.X0 = c.take<float>(pl.x0path ? P * 960 : 0);
+    w.POOLED = c.take<float>(T * cb * emb);
+    w.ENC = c.take<float>(cb * emb);
+    w.D1 = c.take<float>(cb * 256);
+    w.D2a = c.take<float>(cb * 128);
+    w.D2b = c.take<float>(cb * 128);
+    w.D2c = c.take<float>(cb * 128);
+    w.D3a = c.take<float>(cb * 64);
+    w.D3b = c.take<float>(cb * 64);
+    w.D3c = c.take<float>(cb * 64);
+    w.QKV = c.take<float>(cb * 192);
+    w.ATT = c.take<float>(cb * 64);
+    w.bytes = c.bytes();
+    return w;
+}
+
+// one chunk of an fd forward: patches [s, s + cb) of the b in the call
+struct FdChunk {
+    const float* pc;
+    int64_t s, cb, b;
+    int mp;
+    const int32_t* knn_force;
+    void* const* taps;
+    int64_t P() const { return cb * mp; }
+    float* tap(int which) const { return taps ? (float*)taps[which] : nullptr; }
+    float* x0_tap() const { return tap(SAPCU_FD_TAP_X0) ? tap(SAPCU_FD_TAP_X0) + s * mp * 960 : nullptr; }    // this chunk's rows
+};
+
+static const int FD_CIN[4] = {0, 64, 128, 256}, FD_COUT[4] = {64, 128, 256, 512}, FD_COFF[4] = {0, 64, 192, 448};
+
+// the whole encoder up to pooled [T, cb, emb] in ONE launch, one workgroup per patch (fd_encoder.hip)   fd:408-480
+static int fd_encode_fused(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const FdChunk& c, hipStream_t st) {
+    FdEncArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.patch = c.pc; ea.b = c.cb; ea.b_total = c.b; ea.s0 = c.s;
+    ea.m = c.mp; ea.T = m->T; ea.kk = pl.kk; ea.kmax0 = pl.kmax0; ea.nscale = m->nscale; ea.emb = m->emb;
+    for (int i = 0; i < 4; ++i) ea.ks[i] = i < m->nscale ? imin(m->ks[i], c.mp) : 0;
+    ea.e0_w = m->p(FD_E0_W); ea.e0_b = m->p(FD_E0_B);
+    const _Float16* fw = (const _Float16*)m->fde_w;
+    ea.fuse_wp = fw + m->fde_off[0]; ea.fuse_b = m->p(FD_FUSE_B);
+    for (int l = 0; l < 3; ++l) {
+        ea.edge_wp[l] = fw + m->fde_off[1 + l];
+        ea.shift[l] = m->p(FD_EDGE1_SHIFT + 3 * l);
     }
-    add((int64_t)m->T * pl.cb * m->emb, 4); add(pl.cb * m->emb, 4);
-    add(pl.cb * 256, 4);
-    for (int i = 0; i < 3; ++i) add(pl.cb * 128, 4);
-    for (int i = 0; i < 3; ++i) add(pl.cb * 64, 4);
-    add(pl.cb * 192, 4); add(pl.cb * 64, 4);
-    return fl + 256;
+    ea.msc_wp = fw + m->fde_off[4]; ea.msc_b = m->p(FD_MSC_B);
+    ea.nprm = m->fde_nprm;
+    ea.pooled = W.POOLED;
+    ea.knn_force = c.knn_force;
+    ea.tap_knn = (int32_t*)c.tap(SAPCU_FD_TAP_KNN);
+    ea.tap_fused0 = c.tap(SAPCU_FD_TAP_FUSED0);
+    ea.tap_spikes = c.tap(SAPCU_FD_TAP_SPIKES);
+    ea.tap_x0 = c.tap(SAPCU_FD_TAP_X0);
+    ea.gate = m->gate_dev; ea.ovf = m->ovf_dev;
+    return launch_fd_encoder(ea, st);
+}
+
+// multi_scale_conv as a GEMM over the T spike slabs with the max over the points in its epilogue (keys at the head of AGG)
+static GemmArgs fd_msc_gemm_args(const sapcu_model* m, const FdWs& W, const FdChunk& c) {
+    GemmArgs mg;
+    memset(&mg, 0, sizeof(mg));
+    mg.a = W.SPK; mg.r = (int64_t)m->T * c.P(); mg.k = 960; mg.lda = 960; mg.w = m->p(FD_MSC_W); mg.n = m->emb; mg.bias = m->p(FD_MSC_B);
+    mg.c = nullptr; mg.ldc = m->emb; mg.epi = EPI_LRELU_MAX; mg.max_keys = reinterpret_cast<unsigned*>(W.AGG); mg.max_m = c.mp;
+    return mg;
+}
+
+// The per-stage front: block 0 (xyz kNN, EdgeConv x S, scale fusion, EIF over T steps, fd:411-444) and blocks 1..3 (feature-space
+// kNN on the t = 0 spikes, factored EdgeConv, neuron, fd:447-474).  Leaves the 960-channel spikes in SPK (x0 path: x0 in X0 and
+// step 0 only) and says in split_spikes whether SPK holds split rows.
+static int fd_front(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const FdChunk& c, bool& split_spikes, hipStream_t st) {
+    const int T = m->T, mp = c.mp;
+    const int64_t P = c.P(), cb = c.cb, s = c.s, b = c.b;
+    void* const* taps = c.taps;
+    // all scales are prefixes of the sorted top-kmax list
+    SAPCU_TRY(launch_patch_knn(c.pc, cb, mp, 3, 3, pl.kmax0, W.idx0, st));
+    SAPCU_TRY(launch_fd_edge0(c.pc, W.idx0, pl.kmax0, P, mp, m->nscale, m->ks_dev, m->p(FD_E0_W), m->p(FD_E0_B), W.E0, st));
+    SAPCU_TRY(gemm(m, W.E0, P, 64 * m->nscale, 64 * m->nscale, m->p(FD_FUSE_W), 64, m->p(FD_FUSE_B), W.FUSED, 64, EPI_LRELU, st));
+    SAPCU_TRY(tap_copy(taps, SAPCU_FD_TAP_FUSED0, s * mp * 64 * 4, W.FUSED, P * 64 * 4, st));
+    float* const X0T = c.x0_tap();
+    if (X0T) SAPCU_CHECK_HIP(hipMemcpy2DAsync(X0T, 960 * 4, W.FUSED, 64 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
+    // multi_scale_conv's operand: split rows written by the neuron kernels themselves (the GEMM then streams them by LDS-DMA
+    // on the big-tile kernel and takes the max over the points in its epilogue) whenever that kernel takes the shape; the
+    // step-0 spikes also go to F0 as f32 for the next blocks' neighbour search and EdgeConv.  Otherwise (tiny batches,
+    // SAPCU_GEMM=f32, SAPCU_FD_MAXFUSE=0 / SAPCU_FD_SPLIT=0, or a caller asking for the spike tap): f32 spikes for all steps.
+    split_spikes = pl.x0path;                               // x0 path: ONE slab of step-0 split rows (the EdgeConv GEMMs' operand)
+    if (!pl.x0path && pl.maxfuse && m->opt_fd_split && !c.tap(SAPCU_FD_TAP_SPIKES)) {
+        GemmArgs probe = fd_msc_gemm_args(m, W, c);
+        probe.a_split = 1;
+        probe.w16_hi = (const _Float16*)m->w16_hi + (probe.w - m->blob);
+        probe.w16_lo = (const _Float16*)m->w16_lo + (probe.w - m->blob);
+        split_spikes = split_rows_gemm_on_big_tile(probe, m->opt_bt);     // (the ring kernel has no max-over-rows epilogue)
+    }
+    float* const SPKS = split_spikes ? W.SPK : nullptr;     // [T*P, 960] split rows (same buffer, other format)
+    float* const SPK0 = split_spikes ? W.F0 : W.SPK;        // where the step-0 f32 spikes live ([P, 960] slab)
+    float* const X0P = pl.x0path ? W.X0 : nullptr;          // the neuron kernels then write x0 and run step 0 only
+    SAPCU_TRY(launch_fd_neuron(true, 0, W.FUSED, 64, nullptr, 0, mp, nullptr, P, 64, m->p(FD_SNN0), T, SPK0, 960, 0,
+                               nullptr, m->gate_dev, st, SPKS, X0P));
+    for (int l = 1; l <= 3; ++l) {
+        const int cin = FD_CIN[l], cout = FD_COUT[l], coff = FD_COFF[l - 1];
+        int32_t* idl = W.idxb + (int64_t)(l - 1) * pl.cb * mp * pl.kk;
+        const float* F = SPK0 + coff;          // t = 0 slab, row stride 960
+        if (c.knn_force) {
+            SAPCU_CHECK_HIP(hipMemcpyAsync(idl, c.knn_force + ((int64_t)(l - 1) * b + s) * mp * pl.kk, P * pl.kk * 4,
+                                           hipMemcpyDeviceToDevice, st));
+        } else {
+            SAPCU_TRY(launch_patch_knn_strided(F, cb, (int64_t)mp * 960, mp, cin, 960, pl.kk, idl, st));
+        }
+        if (c.tap(SAPCU_FD_TAP_KNN))
+            SAPCU_CHECK_HIP(hipMemcpyAsync((int32_t*)taps[SAPCU_FD_TAP_KNN] + ((int64_t)(l - 1) * b + s) * mp * pl.kk,
+                                           idl, P * pl.kk * 4, hipMemcpyDeviceToDevice, st));
+        const int ew = FD_EDGE1_W + 3 * (l - 1);
+        // the factored EdgeConv's GEMM reads the step-0 spikes as split rows when the neuron kernels wrote them (rows 0..P-1 of
+        // SPKS, same pitch and column offsets as the f32 slab): the all-DMA kernels instead of the f32-operand one, same sums
+        if (split_spikes)
+            SAPCU_TRY(gemm(m, SPKS + coff, P, cin, 960, m->p(ew), 2 * cout, nullptr, W.AB, 2 * cout, EPI_BIAS, st, nullptr, 0, nullptr, 0,
+                           1));
+        else
+            SAPCU_TRY(gemm(m, F, P, cin, 960, m->p(ew), 2 * cout, nullptr, W.AB, 2 * cout, EPI_BIAS, st));
+        SAPCU_TRY(launch_fd_neuron(l == 1, 1, W.AB, 2 * cout, idl, pl.kk, mp, m->p(ew + 1), P, cout, m->p(ew + 2), T, SPK0, 960,
+                                   FD_COFF[l], nullptr, m->gate_dev, st, SPKS, X0P));
+        if (X0T && !pl.x0path)
+            SAPCU_TRY(launch_fd_pre(W.AB, 2 * cout, idl, pl.kk, mp, m->p(ew + 1), P, cout, X0T, 960, FD_COFF[l], st));
+    }
+    return SAPCU_OK;
+}
+
+// multi_scale_conv over all T steps + max over the points straight from x0: every spike regenerated on the CU (fd_msc_kernel)
+static int fd_msc_from_x0(const sapcu_model* m, const FdWs& W, const FdChunk& c, hipStream_t st) {
+    if (c.x0_tap()) SAPCU_CHECK_HIP(hipMemcpyAsync(c.x0_tap(), W.X0, (size_t)c.P() * 960 * 4, hipMemcpyDeviceToDevice, st));
+    FdMscArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.x0 = W.X0; ma.b = c.cb; ma.b_total = c.b; ma.s0 = c.s; ma.m = c.mp; ma.T = m->T; ma.emb = m->emb;
+    ma.msc_wp = (const _Float16*)m->fde_w + m->fde_off[4]; ma.msc_b = m->p(FD_MSC_B); ma.nprm = m->fde_nprm;
+    ma.pooled = W.POOLED; ma.tap_spikes = c.tap(SAPCU_FD_TAP_SPIKES); ma.gate = m->gate_dev;
+    return launch_fd_msc(ma, st);
+}
+
+// multi_scale_conv + BN + LeakyReLU over all T*P rows of the spike slabs, max over points        fd:476-480
+static int fd_msc_from_slabs(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const FdChunk& c, bool split_spikes, hipStream_t st) {
+    const int T = m->T, emb = m->emb;
+    const int64_t P = c.P();
+    if (c.tap(SAPCU_FD_TAP_SPIKES)) {
+        for (int t = 0; t < T; ++t)
+            SAPCU_CHECK_HIP(hipMemcpyAsync(c.tap(SAPCU_FD_TAP_SPIKES) + ((int64_t)t * c.b + c.s) * c.mp * 960,
+                                           W.SPK + (int64_t)t * P * 960, P * 960 * 4, hipMemcpyDeviceToDevice, st));
+    }
+    if (pl.maxfuse) {
+        // the max over the patch's points inside the GEMM's epilogue (integer atomicMax on order-preserving keys): the
+        // [T*P, emb] aggregate is never written.  The key buffer is the head of the (otherwise unused) AGG area.
+        GemmArgs mg = fd_msc_gemm_args(m, W, c);
+        SAPCU_CHECK_HIP(hipMemsetAsync(mg.max_keys, 0, (size_t)T * c.cb * emb * 4, st));
+        mg.a_split = split_spikes ? 1 : 0;
+        SAPCU_TRY(run_gemm(m, mg, st));
+        return launch_decode_max_keys(mg.max_keys, (int64_t)T * c.cb * emb, W.POOLED, st);
+    }
+    SAPCU_TRY(gemm(m, W.SPK, (int64_t)T * P, 960, 960, m->p(FD_MSC_W), emb, m->p(FD_MSC_B), W.AGG, emb, EPI_LRELU, st));
+    return launch_rowgroup_max(W.AGG, (int64_t)T * c.cb, c.mp, emb, W.POOLED, st);
+}
+
+// pooled [T, cb, emb] -> temporal integration -> decoder -> distances (every encoder path ends here)
+static int fd_temporal_decoder(const sapcu_model* m, const FdWs& W, const FdChunk& c, float* dist, hipStream_t st) {
+    const int T = m->T, emb = m->emb;
+    const int64_t cb = c.cb, s = c.s;
+    if (c.tap(SAPCU_FD_TAP_POOLED)) {
+        for (int t = 0; t < T; ++t)
+            SAPCU_CHECK_HIP(hipMemcpyAsync(c.tap(SAPCU_FD_TAP_POOLED) + ((int64_t)t * c.b + s) * emb, W.POOLED + (int64_t)t * cb * emb,
+                                           cb * emb * 4, hipMemcpyDeviceToDevice, st));
+    }
+    SAPCU_TRY(launch_fd_temporal(W.POOLED, T, cb, emb, m->p(FD_TI_W), m->p(FD_SNNFC), W.ENC, st));
+    SAPCU_TRY(tap_copy(c.taps, SAPCU_FD_TAP_ENC, s * emb * 4, W.ENC, cb * emb * 4, st));
+    // decoder                                                                    fd:711-725
+    SAPCU_TRY(gemm(m, W.ENC, cb, emb, emb, m->p(FD_FCIN_W), 256, m->p(FD_FCIN_B), W.D1, 256, EPI_GELU, st));
+    SAPCU_TRY(gemm(m, W.D1, cb, 256, 256, m->p(FD_R0_FC0_W), 128, m->p(FD_R0_FC0_B), W.D2a, 128, EPI_GELU, st));
+    SAPCU_TRY(gemm(m, W.D1, cb, 256, 256, m->p(FD_R0_PROJ_W), 128, m->p(FD_R0_PROJ_B), W.D2b, 128, EPI_BIAS, st));
+    SAPCU_TRY(gemm(m, W.D2a, cb, 128, 128, m->p(FD_R0_FC4_W), 128, m->p(FD_R0_FC4_B), W.D2c, 128, EPI_RESID_GELU, st, nullptr, 0, W.D2b,
+                   128));
+    SAPCU_TRY(gemm(m, W.D2c, cb, 128, 128, m->p(FD_R1_FC0_W), 64, m->p(FD_R1_FC0_B), W.D3a, 64, EPI_GELU, st));
+    SAPCU_TRY(gemm(m, W.D2c, cb, 128, 128, m->p(FD_R1_PROJ_W), 64, m->p(FD_R1_PROJ_B), W.D3b, 64, EPI_BIAS, st));
+    SAPCU_TRY(gemm(m, W.D3a, cb, 64, 64, m->p(FD_R1_FC4_W), 64, m->p(FD_R1_FC4_B), W.D3c, 64, EPI_RESID_GELU, st, nullptr, 0, W.D3b, 64));
+    SAPCU_TRY(gemm(m, W.D3c, cb, 64, 64, m->p(FD_QKV_W), 192, m->p(FD_QKV_B), W.QKV, 192, EPI_BIAS, st));
+    return launch_fd_tail(W.D3c, W.QKV, cb, m->heads, m->p(FD_WO_T), m->p(FD_BO), m->p(FD_LN_W), m->p(FD_LN_B), m->p(FD_WH_T),
+                          m->p(FD_BH), m->p(FD_WD), m->p(FD_BD), W.ATT, dist + s, st);
 }
 
 static int fd_forward(const sapcu_model* m, const float* patch, int64_t b, int mp, const int32_t* knn_force,
                       float* dist, void* ws, int64_t ws_bytes, void* const* taps, hipStream_t st) {
     const FdPlan pl = fd_plan(m, b, mp);
-    if (ws_bytes < fd_ws_bytes(m, b, mp)) {
-        set_error("fd_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)fd_ws_bytes(m, b, mp));
+    const FdWs W = fd_ws_layout(ws_align256(ws), m, pl, mp);
+    if (ws_bytes < (int64_t)W.bytes + 256) {
+        set_error("fd_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)W.bytes + 256);
         return SAPCU_ERR_WORKSPACE;
     }
-    const int T = m->T, emb = m->emb;
-    static const int cin[4] = {0, 64, 128, 256}, cout[4] = {64, 128, 256, 512}, coff[4] = {0, 64, 192, 448};
     for (int64_t s = 0; s < b; s += pl.cb) {
-        const int64_t cb = (b - s) < pl.cb ? (b - s) : pl.cb;
-        const int64_t P = cb * mp;
-        Arena A{(char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255), ws_bytes, 0};
-        // per-point intermediates exist only on the per-stage path (the fused encoder keeps them on the CU)
-        const int64_t pp = pl.fused ? 0 : 1;
-        int32_t* idx0 = A.take<int32_t>(pp * pl.cb * mp * pl.kmax0);
-        int32_t* idxb = A.take<int32_t>(pp * 3 * pl.cb * mp * pl.kk);
-        float* E0 = A.take<float>(pp * pl.cb * mp * 64 * m->nscale);
-        float* FUSED = A.take<float>(pp * pl.cb * mp * 64);
-        float* SPK = A.take<float>(pp * (pl.x0path ? 1 : (int64_t)T) * pl.cb * mp * 960);
-        float* F0 = A.take<float>(pp * pl.cb * mp * 960);
-        float* AB = A.take<float>(pp * pl.cb * mp * 1024);
-        float* AGG = A.take<float>(pp * (int64_t)T * pl.cb * pl.agg_rows(mp) * emb);       // maxfuse: T*cb*emb keys only
-        float* X0 = A.take<float>(pl.x0path ? pl.cb * mp * 960 : 0);                       // x0 path: [P, 960] pre-activations
-        float* POOLED = A.take<float>((int64_t)T * pl.cb * emb);
-        float* ENC = A.take<float>(pl.cb * emb);
-        float* D1 = A.take<float>(pl.cb * 256);
-        float* D2a = A.take<float>(pl.cb * 128);
-        float* D2b = A.take<float>(pl.cb * 128);
-        float* D2c = A.take<float>(pl.cb * 128);
-        float* D3a = A.take<float>(pl.cb * 64);
-        float* D3b = A.take<float>(pl.cb * 64);
-        float* D3c = A.take<float>(pl.cb * 64);
-        float* QKV = A.take<float>(pl.cb * 192);
-        float* ATT = A.take<float>(pl.cb * 64);
-        const float* pc = patch + s * mp * 3;
-
+        const FdChunk c{patch + s * mp * 3, s, (b - s) < pl.cb ? (b - s) : pl.cb, b, mp, knn_force, taps};
         if (pl.fused) {
-            // the whole encoder up to pooled [T, cb, emb] in ONE launch, one workgroup per patch (fd_encoder.hip)   fd:408-480
-            FdEncArgs ea;
-            memset(&ea, 0, sizeof(ea));
-            ea.patch = pc; ea.b = cb; ea.b_total = b; ea.s0 = s;
-            ea.m = mp; ea.T = T; ea.kk = pl.kk; ea.kmax0 = pl.kmax0; ea.nscale = m->nscale; ea.emb = emb;
-            for (int i = 0; i < 4; ++i) ea.ks[i] = i < m->nscale ? imin(m->ks[i], mp) : 0;
-            ea.e0_w = m->p(FD_E0_W); ea.e0_b = m->p(FD_E0_B);
-            const _Float16* fw = (const _Float16*)m->fde_w;
-            ea.fuse_wp = fw + m->fde_off[0]; ea.fuse_b = m->p(FD_FUSE_B);
-            for (int l = 0; l < 3; ++l) {
-                ea.edge_wp[l] = fw + m->fde_off[1 + l];
-                ea.shift[l] = m->p(FD_EDGE1_SHIFT + 3 * l);
-            }
-            ea.msc_wp = fw + m->fde_off[4]; ea.msc_b = m->p(FD_MSC_B);
-            ea.nprm = m->fde_nprm;
-            ea.pooled = POOLED;
-            ea.knn_force = knn_force;
-            ea.tap_knn = taps ? (int32_t*)taps[SAPCU_FD_TAP_KNN] : nullptr;
-            ea.tap_fused0 = taps ? (float*)taps[SAPCU_FD_TAP_FUSED0] : nullptr;
-            ea.tap_spikes = taps ? (float*)taps[SAPCU_FD_TAP_SPIKES] : nullptr;
-            ea.tap_x0 = taps ? (float*)taps[SAPCU_FD_TAP_X0] : nullptr;
-            ea.gate = m->gate_dev; ea.ovf = m->ovf_dev;
-            SAPCU_TRY(launch_fd_encoder(ea, st));
+            SAPCU_TRY(fd_encode_fused(m, pl, W, c, st));
         } else {
-        // block 0: xyz kNN (all scales are prefixes of the sorted top-kmax list), EdgeConv x S,
-        // scale fusion, EIF over T steps                                           fd:411-444
-        SAPCU_TRY(launch_patch_knn(pc, cb, mp, 3, 3, pl.kmax0, idx0, st));
-        SAPCU_TRY(launch_fd_edge0(pc, idx0, pl.kmax0, P, mp, m->nscale, m->ks_dev, m->p(FD_E0_W), m->p(FD_E0_B), E0, st));
-        SAPCU_TRY(gemm(m, E0, P, 64 * m->nscale, 64 * m->nscale, m->p(FD_FUSE_W), 64, m->p(FD_FUSE_B), FUSED, 64,
-                       EPI_LRELU, st));
-        SAPCU_TRY(tap_copy(taps, SAPCU_FD_TAP_FUSED0, s * mp * 64 * 4, FUSED, P * 64 * 4, st));
-        float* const X0T = (taps && taps[SAPCU_FD_TAP_X0]) ? (float*)taps[SAPCU_FD_TAP_X0] + s * mp * 960 : nullptr;
-        if (X0T) SAPCU_CHECK_HIP(hipMemcpy2DAsync(X0T, 960 * 4, FUSED, 64 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
-        // multi_scale_conv's operand: split rows written by the neuron kernels themselves (the GEMM then streams them by LDS-DMA
-        // on the big-tile kernel and takes the max over the points in its epilogue) whenever that kernel takes the shape; the
-        // step-0 spikes also go to F0 as f32 for the next blocks' neighbour search and EdgeConv.  Otherwise (tiny batches,
-        // SAPCU_GEMM=f32, SAPCU_FD_MAXFUSE=0 / SAPCU_FD_SPLIT=0, or a caller asking for the spike tap): f32 spikes for all steps.
-        GemmArgs mg;
-        memset(&mg, 0, sizeof(mg));
-        mg.a = SPK; mg.r = (int64_t)T * P; mg.k = 960; mg.lda = 960; mg.w = m->p(FD_MSC_W); mg.n = emb; mg.bias = m->p(FD_MSC_B);
-        mg.c = nullptr; mg.ldc = emb; mg.epi = EPI_LRELU_MAX; mg.max_keys = reinterpret_cast<unsigned*>(AGG); mg.max_m = mp;
-        const bool maxfuse = pl.maxfuse;
-        bool split_spikes = pl.x0path;                          // x0 path: ONE slab of step-0 split rows (the EdgeConv GEMMs' operand)
-        if (!pl.x0path && maxfuse && m->opt_fd_split && !(taps && taps[SAPCU_FD_TAP_SPIKES])) {
-            GemmArgs probe = mg;
-            probe.a_split = 1;
-            probe.w16_hi = (const _Float16*)m->w16_hi + (mg.w - m->blob);
-            probe.w16_lo = (const _Float16*)m->w16_lo + (mg.w - m->blob);
-            split_spikes = split_rows_gemm_on_big_tile(probe, m->opt_bt);     // (the ring kernel has no max-over-rows epilogue)
+            bool split_spikes = false;
+            SAPCU_TRY(fd_front(m, pl, W, c, split_spikes, st));
+            SAPCU_TRY(pl.x0path ? fd_msc_from_x0(m, W, c, st) : fd_msc_from_slabs(m, pl, W, c, split_spikes, st));
         }
-        float* const SPKS = split_spikes ? SPK : nullptr;       // [T*P, 960] split rows (same buffer, other format)
-        float* const SPK0 = split_spikes ? F0 : SPK;            // where the step-0 f32 spikes live ([P, 960] slab)
-        float* const X0P = pl.x0path ? X0 : nullptr;            // the neuron kernels then write x0 and run step 0 only
-        SAPCU_TRY(launch_fd_neuron(true, 0, FUSED, 64, nullptr, 0, mp, nullptr, P, 64, m->p(FD_SNN0), T, SPK0, 960, 0,
-                                   nullptr, m->gate_dev, st, SPKS, X0P));
-        // blocks 1..3: feature-space kNN on the t=0 spikes, factored EdgeConv, neuron  fd:447-474
-        for (int l = 1; l <= 3; ++l) {
-            int32_t* idl = idxb + (int64_t)(l - 1) * pl.cb * mp * pl.kk;
-            const float* F = SPK0 + coff[l - 1];   // t = 0 slab, row stride 960
-            if (knn_force) {
-                SAPCU_CHECK_HIP(hipMemcpyAsync(idl, knn_force + ((int64_t)(l - 1) * b + s) * mp * pl.kk, P * pl.kk * 4,
-                                               hipMemcpyDeviceToDevice, st));
-            } else {
-                SAPCU_TRY(launch_patch_knn_strided(F, cb, (int64_t)mp * 960, mp, cin[l], 960, pl.kk, idl, st));
-            }
-            if (taps && taps[SAPCU_FD_TAP_KNN])
-                SAPCU_CHECK_HIP(hipMemcpyAsync((int32_t*)taps[SAPCU_FD_TAP_KNN] + ((int64_t)(l - 1) * b + s) * mp * pl.kk,
-                                               idl, P * pl.kk * 4, hipMemcpyDeviceToDevice, st));
-            const int ew = FD_EDGE1_W + 3 * (l - 1);
-            // the factored EdgeConv's GEMM reads the step-0 spikes as split rows when the neuron kernels wrote them (rows 0..P-1 of
-            // SPKS, same pitch and column offsets as the f32 slab): the all-DMA kernels instead of the f32-operand one, same sums
-            if (split_spikes)
-                SAPCU_TRY(gemm(m, SPKS + coff[l - 1], P, cin[l], 960, m->p(ew), 2 * cout[l], nullptr, AB, 2 * cout[l], EPI_BIAS, st,
-                               nullptr, 0, nullptr, 0, 1));
-            else
-                SAPCU_TRY(gemm(m, F, P, cin[l], 960, m->p(ew), 2 * cout[l], nullptr, AB, 2 * cout[l], EPI_BIAS, st));
-            SAPCU_TRY(launch_fd_neuron(l == 1, 1, AB, 2 * cout[l], idl, pl.kk, mp, m->p(ew + 1), P, cout[l], m->p(ew + 2),
-                                       T, SPK0, 960, coff[l], nullptr, m->gate_dev, st, SPKS, X0P));
-            if (X0T && !pl.x0path) SAPCU_TRY(launch_fd_pre(AB, 2 * cout[l], idl, pl.kk, mp, m->p(ew + 1), P, cout[l], X0T, 960, coff[l], st));
-        }
-        if (pl.x0path) {
-            // multi_scale_conv over all T steps + max over the points straight from x0: every spike regenerated on the CU (fd_msc_kernel)
-            if (X0T) SAPCU_CHECK_HIP(hipMemcpyAsync(X0T, X0, (size_t)P * 960 * 4, hipMemcpyDeviceToDevice, st));
-            FdMscArgs ma;
-            memset(&ma, 0, sizeof(ma));
-            ma.x0 = X0; ma.b = cb; ma.b_total = b; ma.s0 = s; ma.m = mp; ma.T = T; ma.emb = emb;
-            ma.msc_wp = (const _Float16*)m->fde_w + m->fde_off[4]; ma.msc_b = m->p(FD_MSC_B); ma.nprm = m->fde_nprm;
-            ma.pooled = POOLED; ma.tap_spikes = taps ? (float*)taps[SAPCU_FD_TAP_SPIKES] : nullptr; ma.gate = m->gate_dev;
-            SAPCU_TRY(launch_fd_msc(ma, st));
-        } else {
-        if (taps && taps[SAPCU_FD_TAP_SPIKES]) {
-            for (int t = 0; t < T; ++t)
-                SAPCU_CHECK_HIP(hipMemcpyAsync((float*)taps[SAPCU_FD_TAP_SPIKES] + ((int64_t)t * b + s) * mp * 960,
-                                               SPK + (int64_t)t * P * 960, P * 960 * 4, hipMemcpyDeviceToDevice, st));
-        }
-        // multi_scale_conv + BN + LeakyReLU over all T*P rows, max over points        fd:476-480
-        if (maxfuse) {
-            // the max over the patch's points inside the GEMM's epilogue (integer atomicMax on order-preserving keys): the
-            // [T*P, emb] aggregate is never written.  The key buffer is the head of the (otherwise unused) AGG area.
-            SAPCU_CHECK_HIP(hipMemsetAsync(mg.max_keys, 0, (size_t)T * cb * emb * 4, st));
-            mg.a_split = split_spikes ? 1 : 0;
-            SAPCU_TRY(run_gemm(m, mg, st));
-            SAPCU_TRY(launch_decode_max_keys(mg.max_keys, (int64_t)T * cb * emb, POOLED, st));
-        } else {
-            SAPCU_TRY(gemm(m, SPK, (int64_t)T * P, 960, 960, m->p(FD_MSC_W), emb, m->p(FD_MSC_B), AGG, emb, EPI_LRELU, st));
-            SAPCU_TRY(launch_rowgroup_max(AGG, (int64_t)T * cb, mp, emb, POOLED, st));
-        }
-        }   // T spike slabs + GEMM
-        }   // per-stage encoder
-        if (taps && taps[SAPCU_FD_TAP_POOLED]) {
-            for (int t = 0; t < T; ++t)
-                SAPCU_CHECK_HIP(hipMemcpyAsync((float*)taps[SAPCU_FD_TAP_POOLED] + ((int64_t)t * b + s) * emb,
-                                               POOLED + (int64_t)t * cb * emb, cb * emb * 4, hipMemcpyDeviceToDevice, st));
-        }
-        SAPCU_TRY(launch_fd_temporal(POOLED, T, cb, emb, m->p(FD_TI_W), m->p(FD_SNNFC), ENC, st));
-        SAPCU_TRY(tap_copy(taps, SAPCU_FD_TAP_ENC, s * emb * 4, ENC, cb * emb * 4, st));
-        // decoder                                                                    fd:711-725
-        SAPCU_TRY(gemm(m, ENC, cb, emb, emb, m->p(FD_FCIN_W), 256, m->p(FD_FCIN_B), D1, 256, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, D1, cb, 256, 256, m->p(FD_R0_FC0_W), 128, m->p(FD_R0_FC0_B), D2a, 128, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, D1, cb, 256, 256, m->p(FD_R0_PROJ_W), 128, m->p(FD_R0_PROJ_B), D2b, 128, EPI_BIAS, st));
-        SAPCU_TRY(gemm(m, D2a, cb, 128, 128, m->p(FD_R0_FC4_W), 128, m->p(FD_R0_FC4_B), D2c, 128, EPI_RESID_GELU, st,
-                       nullptr, 0, D2b, 128));
-        SAPCU_TRY(gemm(m, D2c, cb, 128, 128, m->p(FD_R1_FC0_W), 64, m->p(FD_R1_FC0_B), D3a, 64, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, D2c, cb, 128, 128, m->p(FD_R1_PROJ_W), 64, m->p(FD_R1_PROJ_B), D3b, 64, EPI_BIAS, st));
-        SAPCU_TRY(gemm(m, D3a, cb, 64, 64, m->p(FD_R1_FC4_W), 64, m->p(FD_R1_FC4_B), D3c, 64, EPI_RESID_GELU, st, nullptr,
-                       0, D3b, 64));
-        SAPCU_TRY(gemm(m, D3c, cb, 64, 64, m->p(FD_QKV_W), 192, m->p(FD_QKV_B), QKV, 192, EPI_BIAS, st));
-        SAPCU_TRY(launch_fd_tail(D3c, QKV, cb, m->heads, m->p(FD_WO_T), m->p(FD_BO), m->p(FD_LN_W), m->p(FD_LN_B),
-                                 m->p(FD_WH_T), m->p(FD_BH), m->p(FD_WD), m->p(FD_BD), ATT, dist + s, st));
+        SAPCU_TRY(fd_temporal_decoder(m, W, c, dist, st));
     }
     return SAPCU_OK;
 }
@@ -855,14 +947,34 @@ int sapcu_posenc_gemm_f32(const float* pe1, int64_t r, int d, const float* w, co
     return launch_gemm(g, (hipStream_t)stream);
 }
 
+// workspace of sapcu_fn_edge_chain_f32 (base: the caller's pointer aligned up, or null for the size; the sizer adds 256 bytes)
+struct ChainWs {
+    int2* tab;               // [points * kk] edge table
+    float4* pd;              // [points * kk] position differences
+    char* split[3];          // per matrix: hi | lo | overflow counter
+    _Float16* packed[3];     // per matrix: MFMA-fragment order
+    size_t bytes;
+};
+
+static ChainWs chain_ws_layout(void* base, int64_t points, int d, int kk) {
+    WsCarver c(base);
+    ChainWs w;
+    w.tab = c.take<int2>(points * kk);
+    w.pd = c.take<float4>(points * kk);
+    for (int q = 0; q < 3; ++q) {
+        w.split[q] = c.take<char>((int64_t)d * d * 4 + 16);
+        w.packed[q] = c.take<_Float16>((int64_t)d * d * 2);
+    }
+    w.bytes = c.bytes();
+    return w;
+}
+
 int64_t sapcu_fn_edge_chain_workspace_bytes(int64_t points, int d, int kk) {
     if (points < 0 || !fn_edge_chain_ok(d, kk)) {
         set_error("fn_edge_chain_workspace_bytes: unsupported shape (d=%d kk=%d)", d, kk);
         return SAPCU_ERR_ARG;
     }
-    const int64_t rows = points * kk;
-    auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-    return up(rows * 8) + up(rows * 16) + 3 * (up((int64_t)d * d * 4 + 16) + up((int64_t)d * d * 4)) + 256;
+    return (int64_t)chain_ws_layout(nullptr, points, d, kk).bytes + 256;
 }
 
 int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t points, int m_pts, int d, int kk,
@@ -880,30 +992,24 @@ int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t poin
         return SAPCU_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    Arena A{(char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), workspace_bytes, 0};
-    int2* tab = A.take<int2>(points * kk);
-    float4* pd = A.take<float4>(points * kk);
+    const ChainWs W = chain_ws_layout(ws_align256(workspace), points, d, kk);
     const float* ws[3] = {w1, w2, w3};
-    const _Float16* packed[3];
     for (int q = 0; q < 3; ++q) {
-        char* split = A.take<char>((int64_t)d * d * 4 + 16);              // hi | lo | overflow counter
-        _Float16* pk = A.take<_Float16>((int64_t)d * d * 2);
         GemmArgs g;
         memset(&g, 0, sizeof(g));
-        SAPCU_TRY(split_into_ws(ws[q], (int64_t)d * d, split, g, st));
-        SAPCU_TRY(launch_pack_chain_weights(g.w16_hi, g.w16_lo, d, pk, st));
-        packed[q] = pk;
+        SAPCU_TRY(split_into_ws(ws[q], (int64_t)d * d, W.split[q], g, st));
+        SAPCU_TRY(launch_pack_chain_weights(g.w16_hi, g.w16_lo, d, W.packed[q], st));
     }
     ChainArgs ca;
     memset(&ca, 0, sizeof(ca));
     ca.P = points; ca.m = m_pts; ca.qkv = qkv; ca.ldq = 3 * d;
     ca.wd = w_delta; ca.bd = b_delta; ca.lifd = lif_delta;
-    ca.w1p = packed[0]; ca.b1 = b1; ca.lif1 = lif1;
-    ca.w2p = packed[1]; ca.b2 = b2; ca.lif2 = lif2;
-    ca.w3p = packed[2]; ca.b3 = b3;
+    ca.w1p = W.packed[0]; ca.b1 = b1; ca.lif1 = lif1;
+    ca.w2p = W.packed[1]; ca.b2 = b2; ca.lif2 = lif2;
+    ca.w3p = W.packed[2]; ca.b3 = b3;
     ca.inv_sqrt_hd = 1.0f / (float)sqrt((double)(d / heads));
     ca.res = res_out; ca.res_split = 0; ca.T = lif_steps;
-    return launch_fn_edge_chain(ca, patch, idx, d, kk, tab, pd, st);
+    return launch_fn_edge_chain(ca, patch, idx, d, kk, W.tab, W.pd, st);
 }
 
 int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob, int64_t blob_floats,
@@ -912,39 +1018,7 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
     sapcu_model* m = new (std::nothrow) sapcu_model();
     SAPCU_CHECK_ARG(m != nullptr, "model_create: out of host memory");
     m->kind = kind;
-    m->ks_dev = nullptr;
-    m->gate_dev = nullptr;
-    m->blob = nullptr;
-    m->w16_hi = nullptr;
-    m->w16_lo = nullptr;
-    m->chain_w = nullptr;
-    m->ovf_dev = nullptr;
-    m->fde_w = nullptr;
-    m->fde_nprm = nullptr;
-    const char* ge = getenv("SAPCU_GEMM");
-    m->sf16 = !(ge && strcmp(ge, "f32") == 0);
-    m->opt_bt = !env_off("SAPCU_BT");
-    m->opt_chain = !env_off("SAPCU_CHAIN");
-    {
-        const char* v = getenv("SAPCU_CHAIN");
-        m->opt_chain_wide = v && strcmp(v, "wide") == 0;
-    }
-    m->opt_fn_maxfuse = !env_off("SAPCU_FN_MAXFUSE");
-    m->opt_fn_fold_out = !env_off("SAPCU_FN_FOLD_OUT");
-    for (int l = 0; l < 3; ++l) m->fold_w[l] = m->fold_b[l] = 0;
-    m->opt_fd_maxfuse = !env_off("SAPCU_FD_MAXFUSE");
-    m->opt_fd_split = !env_off("SAPCU_FD_SPLIT");
-    m->opt_fd_fused = !env_off("SAPCU_FD_FUSED");
-    m->opt_fd_x0 = !env_off("SAPCU_FD_X0");
-    const char* ce = getenv("SAPCU_CHUNK");
-    m->chunk = ce ? atoll(ce) : 0;
-    if (m->chunk < 0) m->chunk = 0;
-    // workspace budget per forward (the caller owns the buffer; sapcu_workspace_bytes reports what a batch needs under it):
-    // 20 GiB holds the whole 4096-patch benchmark batch at M = 48 in one chunk (16.9 GB fn, 6.7 GB fd) and cuts the reference's
-    // default M = 100 (8.5 MB per patch) into chunks of ~2400 patches instead of a 35 GB workspace
-    const char* be = getenv("SAPCU_WS_BUDGET_MB");
-    m->ws_budget = (be ? atoll(be) : 20480) * (int64_t)(1 << 20);
-    if (m->ws_budget < (int64_t)(64 << 20)) m->ws_budget = (int64_t)(64 << 20);
+    read_env_switches(m);
     int rc = SAPCU_OK;
     if (kind == SAPCU_KIND_FN) {
         if (n_hp != 6 || n_dir != FN_SLOTS) {
@@ -1050,18 +1124,15 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
             }
             // fn blocks 1-3 (d = 128, 256, 512): the three d x d matrices of the edge chain again in MFMA-fragment order
             if (rc == SAPCU_OK && m->sf16 && kind == SAPCU_KIND_FN) {
-                const int64_t halves = (int64_t)3 * 2 * (128 * 128 + 256 * 256 + 512 * 512);
-                hip_ok(hipMalloc(&m->chain_w, (size_t)halves * 2), "hipMalloc(chain_w)");
-                int64_t off = 0;
+                hip_ok(hipMalloc(&m->chain_w, (size_t)chain_w_off(3, 0) * 2), "hipMalloc(chain_w)");
                 for (int l = 0; l < 3 && rc == SAPCU_OK; ++l) {
                     const int d = 128 << l;
                     static const int slots[3] = {B_DELTA2_W, B_GAMMA_W, B_GAMMA2_W};
                     for (int q = 0; q < 3 && rc == SAPCU_OK; ++q) {
                         const int64_t wo = m->dir[FN_BLK0 + l * B_SLOTS + slots[q]];
                         if (launch_pack_chain_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, d,
-                                                      (_Float16*)m->chain_w + off, nullptr) != SAPCU_OK)
+                                                      (_Float16*)m->chain_w + chain_w_off(l, q), nullptr) != SAPCU_OK)
                             rc = SAPCU_ERR_HIP;
-                        off += (int64_t)d * d * 2;
                     }
                 }
                 if (rc == SAPCU_OK) hip_ok(hipDeviceSynchronize(), "pack chain weights");
@@ -1100,16 +1171,7 @@ int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob,
         }
     }
     if (rc != SAPCU_OK) {
-        if (m->w16_hi) (void)hipFree(m->w16_hi);
-        if (m->w16_lo) (void)hipFree(m->w16_lo);
-        if (m->chain_w) (void)hipFree(m->chain_w);
-        if (m->ovf_dev) (void)hipFree(m->ovf_dev);
-        if (m->blob) (void)hipFree(m->blob);
-        if (m->ks_dev) (void)hipFree(m->ks_dev);
-        if (m->gate_dev) (void)hipFree(m->gate_dev);
-        if (m->fde_w) (void)hipFree(m->fde_w);
-        if (m->fde_nprm) (void)hipFree(m->fde_nprm);
-        delete m;
+        free_model(m);
         return rc;
     }
     *out = m;
@@ -1127,16 +1189,7 @@ int sapcu_internal_fold_affine_host(const float* w_out, const float* b_out, cons
 
 int sapcu_model_destroy(sapcu_model_t m) {
     if (!m) return SAPCU_OK;
-    if (m->w16_hi) (void)hipFree(m->w16_hi);
-    if (m->w16_lo) (void)hipFree(m->w16_lo);
-    if (m->chain_w) (void)hipFree(m->chain_w);
-    if (m->ovf_dev) (void)hipFree(m->ovf_dev);
-    if (m->blob) (void)hipFree(m->blob);
-    if (m->ks_dev) (void)hipFree(m->ks_dev);
-    if (m->gate_dev) (void)hipFree(m->gate_dev);
-    if (m->fde_w) (void)hipFree(m->fde_w);
-    if (m->fde_nprm) (void)hipFree(m->fde_nprm);
-    delete m;
+    free_model(m);
     return SAPCU_OK;
 }
 
@@ -1145,7 +1198,10 @@ int64_t sapcu_workspace_bytes(sapcu_model_t m, int64_t b, int m_pts) {
         set_error("workspace_bytes: bad argument");
         return SAPCU_ERR_ARG;
     }
-    return m->kind == SAPCU_KIND_FN ? fn_ws_bytes(m, b, m_pts) : fd_ws_bytes(m, b, m_pts);
+    // the layout on a null base + the bytes the forward's align-up of the caller's pointer may cost
+    const size_t bytes = m->kind == SAPCU_KIND_FN ? fn_ws_layout(nullptr, m, fn_plan(m, b, m_pts), m_pts).bytes
+                                                  : fd_ws_layout(nullptr, m, fd_plan(m, b, m_pts), m_pts).bytes;
+    return (int64_t)bytes + 256;
 }
 
 int sapcu_model_gate_violations(sapcu_model_t m, int* count_host) {

@@ -1,4 +1,4 @@
-// Launchers of patch_ops.hip (host side), used by model.hip and api.hip.
+// Host-side launchers of patch_ops.hip, fn_edge_chain.hip and fd_encoder.hip, used by model.hip and train_ops.hip.
 #pragma once
 #include "common.h"
 

@@ -157,6 +157,26 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ d
 constexpr int64_t BF_WGRAD_SLAB = 512;       // rows per weight-gradient slab (these launches are small: more slabs = more workgroups)
 constexpr int64_t BF_COLSUM_SLAB = 256;      // rows per bias-gradient slab
 
+// workspace of sapcu_conv1x1_wgrad_bf16: the weight-gradient slab partials (none for a single slab, which goes straight to grad_w),
+// then the bias-gradient slab partials, packed.  The caller's pointer is aligned up first; the sizer's slack is 512 bytes.
+struct WgradBf16Ws {
+    int64_t slabs, cslabs;
+    float* part;             // [slabs][n * k], slabs > 1 only
+    float* cpart;            // [cslabs][n]
+    size_t bytes;
+};
+
+static WgradBf16Ws wgrad_bf16_ws_layout(void* base, int64_t rows, int n, int k) {
+    WsCarver c(base, sizeof(float));
+    WgradBf16Ws w;
+    w.slabs = (rows + BF_WGRAD_SLAB - 1) / BF_WGRAD_SLAB;
+    w.cslabs = (rows + BF_COLSUM_SLAB - 1) / BF_COLSUM_SLAB;
+    w.part = c.take<float>(w.slabs > 1 ? w.slabs * (int64_t)n * k : 0);
+    w.cpart = c.take<float>(w.cslabs * (int64_t)n);
+    w.bytes = c.bytes();
+    return w;
+}
+
 }  // namespace sapcu
 
 using namespace sapcu;
@@ -178,8 +198,7 @@ int sapcu_gemm_bf16(const float* a, int64_t r, int k, int lda, const float* w, i
 
 int64_t sapcu_wgrad_bf16_workspace_bytes(int64_t rows, int n, int k) {
     if (rows < 0 || n < 1 || k < 1) return SAPCU_ERR_ARG;
-    const int64_t slabs = (rows + BF_WGRAD_SLAB - 1) / BF_WGRAD_SLAB, cslabs = (rows + BF_COLSUM_SLAB - 1) / BF_COLSUM_SLAB;
-    return (slabs > 1 ? slabs * (int64_t)n * k * 4 : 0) + cslabs * (int64_t)n * 4 + 512;
+    return (int64_t)wgrad_bf16_ws_layout(nullptr, rows, n, k).bytes + 512;
 }
 
 int sapcu_conv1x1_wgrad_bf16(const float* grad_y, int ldy, const float* x, int ldx, int64_t rows, int n, int k, float* grad_w,
@@ -190,17 +209,16 @@ int sapcu_conv1x1_wgrad_bf16(const float* grad_y, int ldy, const float* x, int l
         if (grad_bias) SAPCU_CHECK_HIP(hipMemsetAsync(grad_bias, 0, (size_t)n * sizeof(float), (hipStream_t)stream));
         return SAPCU_OK;
     }
-    const int64_t slabs = (rows + BF_WGRAD_SLAB - 1) / BF_WGRAD_SLAB;
-    const int64_t cslabs_chk = (rows + BF_COLSUM_SLAB - 1) / BF_COLSUM_SLAB;
-    SAPCU_CHECK_ARG(slabs <= 65535 && cslabs_chk <= 65535, "wgrad_bf16: %lld rows exceed the grid limit (65535 slabs of %d rows)",
+    const WgradBf16Ws L = wgrad_bf16_ws_layout(ws_align256(workspace), rows, n, k);
+    const int64_t slabs = L.slabs, cslabs = L.cslabs;
+    SAPCU_CHECK_ARG(slabs <= 65535 && cslabs <= 65535, "wgrad_bf16: %lld rows exceed the grid limit (65535 slabs of %d rows)",
                     (long long)rows, (int)BF_WGRAD_SLAB);
-    if (workspace_bytes < sapcu_wgrad_bf16_workspace_bytes(rows, n, k) || !workspace) {
-        set_error("wgrad_bf16: workspace %lld B < required %lld B", (long long)workspace_bytes,
-                  (long long)sapcu_wgrad_bf16_workspace_bytes(rows, n, k));
+    if (workspace_bytes < (int64_t)L.bytes + 512 || !workspace) {
+        set_error("wgrad_bf16: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)L.bytes + 512);
         return SAPCU_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    float* part = slabs > 1 ? reinterpret_cast<float*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : grad_w;
+    float* part = slabs > 1 ? L.part : grad_w;
     const dim3 grid((unsigned)((n + BF_BM - 1) / BF_BM), (unsigned)((k + BF_BN - 1) / BF_BN), (unsigned)slabs);
     // dw[n, k]: "A" = grad_y columns (m = output channel), "B" = x columns (n = input channel), reduction over the rows
     hipLaunchKernelGGL((gemm_bf16_kernel<true>), grid, dim3(256), 0, st, grad_y, ldy, x, ldx, (int64_t)n, k, rows, BF_WGRAD_SLAB,
@@ -212,8 +230,7 @@ int sapcu_conv1x1_wgrad_bf16(const float* grad_y, int ldy, const float* x, int l
         SAPCU_CHECK_LAUNCH();
     }
     if (grad_bias) {
-        const int64_t cslabs = (rows + BF_COLSUM_SLAB - 1) / BF_COLSUM_SLAB;
-        float* cpart = reinterpret_cast<float*>(((uintptr_t)workspace + 255) & ~(uintptr_t)255) + (slabs > 1 ? slabs * (int64_t)n * k : 0);
+        float* cpart = L.cpart;
         hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)cslabs), dim3(256), 0, st, grad_y, ldy, rows, n,
                            BF_COLSUM_SLAB, cpart);
         SAPCU_CHECK_LAUNCH();

@@ -373,6 +373,33 @@ static int wgrad_slabs(int64_t rows) {                       // ~1024 rows per s
     return (int)(s < 1 ? 1 : (s > 64 ? 64 : s));
 }
 
+// The workspace of sapcu_train_workspace_bytes is used under two views, each from the caller's pointer as given (the sizer is the
+// larger of the two plus 256 bytes): the column reductions' f64 partials and sums, and the f32 weight-gradient slab partials.
+struct ColSumWs {
+    double* partial;         // [col_blocks][2][ch]
+    double* sums;            // [2][ch]
+    size_t bytes;
+};
+static ColSumWs colsum_ws_layout(void* base, int64_t rows, int ch) {
+    WsCarver c(base, sizeof(double));
+    ColSumWs w;
+    w.partial = c.take<double>(col_blocks(rows) * 2 * (int64_t)ch);
+    w.sums = c.take<double>(2 * (int64_t)ch);
+    w.bytes = c.bytes();
+    return w;
+}
+struct WgradWs {
+    float* part;             // [wgrad_slabs][n * k]
+    size_t bytes;
+};
+static WgradWs wgrad_ws_layout(void* base, int64_t rows, int n, int k) {
+    WsCarver c(base, sizeof(float));
+    WgradWs w;
+    w.part = c.take<float>((int64_t)wgrad_slabs(rows) * n * (k > 0 ? k : 1));
+    w.bytes = c.bytes();
+    return w;
+}
+
 // ---- backward of the per-channel softmax over the k neighbours + weighted aggregation (fn/snn_coder.py:379-389):
 //   forward (fn_softmax_agg_kernel): w = softmax_j(a_j / sqrt(hd)), u_j = v[nbr_j] + pe_j, res = sum_j w_j u_j
 //   backward, g = d res:  d pe_j = w_j g;  d v[nbr_j] += w_j g (scatter-add);  d a_j = w_j g (u_j - res) / sqrt(hd)
@@ -653,16 +680,17 @@ int sapcu_lif_train_backward(const float* x, const float* grad_spikes, int64_t r
 
 int64_t sapcu_train_workspace_bytes(int64_t rows, int channels, int k) {
     if (rows < 0 || channels < 1 || k < 0) return -1;
-    const int64_t col = (col_blocks(rows) * 2 + 2) * (int64_t)channels * (int64_t)sizeof(double);
-    const int64_t wg = (int64_t)wgrad_slabs(rows) * channels * (int64_t)(k > 0 ? k : 1) * (int64_t)sizeof(float);
+    const int64_t col = (int64_t)colsum_ws_layout(nullptr, rows, channels).bytes;
+    const int64_t wg = (int64_t)wgrad_ws_layout(nullptr, rows, channels, k).bytes;
     return (col > wg ? col : wg) + 256;
 }
 
 static int column_sums(int mode, const float* a, const float* b, int64_t rows, int ch, const float* mean, const float* invstd,
-                       double* ws, double** sums_out, hipStream_t st) {
+                       void* ws, double** sums_out, hipStream_t st) {
     const int64_t nb = col_blocks(rows);
-    double* partial = ws;
-    double* sums = ws + nb * 2 * (int64_t)ch;
+    const ColSumWs L = colsum_ws_layout(ws, rows, ch);
+    double* partial = L.partial;
+    double* sums = L.sums;
     const dim3 grid((unsigned)(nb > 0 ? nb : 1), (unsigned)((ch + 63) / 64));
     if (nb > 0) {
         if (mode == 0) hipLaunchKernelGGL(col_partial_kernel<0>, grid, dim3(256), 0, st, a, b, rows, ch, mean, invstd, partial);
@@ -682,7 +710,7 @@ int sapcu_bn_train_forward(const float* y, int64_t rows, int channels, const flo
                     "bn_train_forward: bad argument");
     SAPCU_CHECK_ARG(workspace_bytes >= sapcu_train_workspace_bytes(rows, channels, 0), "bn_train_forward: workspace too small");
     double* sums = nullptr;
-    int rc = column_sums(0, y, nullptr, rows, channels, nullptr, nullptr, (double*)workspace, &sums, (hipStream_t)stream);
+    int rc = column_sums(0, y, nullptr, rows, channels, nullptr, nullptr, workspace, &sums, (hipStream_t)stream);
     if (rc != SAPCU_OK) return rc;
     const int64_t total = rows * channels;
     hipLaunchKernelGGL(bn_train_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, rows,
@@ -698,7 +726,7 @@ int sapcu_bn_train_backward(const float* y, const float* grad_z, int64_t rows, i
                         channels >= 1, "bn_train_backward: bad argument");
     SAPCU_CHECK_ARG(workspace_bytes >= sapcu_train_workspace_bytes(rows, channels, 0), "bn_train_backward: workspace too small");
     double* sums = nullptr;
-    int rc = column_sums(1, grad_z, y, rows, channels, mean, invstd, (double*)workspace, &sums, (hipStream_t)stream);
+    int rc = column_sums(1, grad_z, y, rows, channels, mean, invstd, workspace, &sums, (hipStream_t)stream);
     if (rc != SAPCU_OK) return rc;
     const int64_t total = rows * channels;
     hipLaunchKernelGGL(bn_train_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, grad_z,
@@ -721,19 +749,19 @@ int sapcu_conv1x1_wgrad_f32(const float* grad_y, int ldy, const float* x, int ld
     if (grad_bias) {                                   // db = column sums of dY (needs a dense dY for the shared reduction)
         SAPCU_CHECK_ARG(ldy == n, "conv1x1_wgrad: the bias gradient needs ldy == n");
         double* sums = nullptr;
-        int rc = column_sums(0, grad_y, nullptr, rows, n, nullptr, nullptr, (double*)workspace, &sums, st);
+        int rc = column_sums(0, grad_y, nullptr, rows, n, nullptr, nullptr, workspace, &sums, st);
         if (rc != SAPCU_OK) return rc;
         hipLaunchKernelGGL(colsum_to_float_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sums, n, grad_bias);
         SAPCU_CHECK_LAUNCH();
     }
     const int slabs = wgrad_slabs(rows);
+    float* const part = wgrad_ws_layout(workspace, rows, n, k).part;
     const int64_t rps = (((rows + slabs - 1) / slabs) + 1) & ~(int64_t)1;      // even: a slab's row pairs stay inside it
     hipLaunchKernelGGL(wgrad_partial_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((k + 63) / 64), (unsigned)slabs), dim3(256), 0,
-                       st, grad_y, ldy, x, ldx, rows, n, k, rps, (float*)workspace);
+                       st, grad_y, ldy, x, ldx, rows, n, k, rps, part);
     SAPCU_CHECK_LAUNCH();
     const int64_t count = (int64_t)n * k;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, (const float*)workspace, slabs,
-                       count, grad_w);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part, slabs, count, grad_w);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
 }
