@@ -96,6 +96,22 @@ _SEEDS_SIGNATURES = {
 }
 SEEDS_EXPORTS = tuple(_SEEDS_SIGNATURES)
 
+# include/sapcu_fd_train.h: the training ops of fd (additions to the same library, a third table like SEEDS_EXPORTS)
+_FD_TRAIN_SIGNATURES = {
+    "sapcu_fd_neuron_step_forward": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 6 + [c_void_p] * 3 + [c_void_p] + [c_void_p] * 5 +
+                                     [c_void_p]),
+    "sapcu_fd_neuron_step_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "sapcu_fd_neuron_step_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p] * 3 + [c_void_p] * 5 +
+                                      [c_void_p, c_int64, c_void_p]),
+    "sapcu_fd_edge_feature_forward": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sapcu_fd_edge_feature_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "sapcu_fd_bn_stats_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "sapcu_fd_bn_stats": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sapcu_fd_bn_lrelu_max_forward": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "sapcu_fd_bn_lrelu_max_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p]),
+}
+FD_TRAIN_EXPORTS = tuple(_FD_TRAIN_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -117,7 +133,8 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
+            list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

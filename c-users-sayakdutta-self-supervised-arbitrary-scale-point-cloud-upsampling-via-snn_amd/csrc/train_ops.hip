@@ -608,6 +608,23 @@ __global__ __launch_bounds__(256) void group_max_bwd_kernel(const float* __restr
     gx[t] = arg[g * c + cc] == i ? gout[g * c + cc] : 0.f;
 }
 
+// The f64 fixed-order column sums (sum, sum of squares) for fd_train_ops.hip (ops.h): sums_out [2][ch] lies inside `ws`, which
+// holds train_column_sums_bytes.  The same two launches as the MODE 0 reduction of sapcu_bn_train_forward.
+int64_t train_column_sums_bytes(int64_t rows, int ch) { return (int64_t)colsum_ws_layout(nullptr, rows, ch).bytes; }
+int train_column_sums(const float* a, int64_t rows, int ch, void* ws, double** sums_out, hipStream_t st) {
+    const int64_t nb = col_blocks(rows);
+    const ColSumWs L = colsum_ws_layout(ws, rows, ch);
+    if (nb > 0) {
+        hipLaunchKernelGGL(col_partial_kernel<0>, dim3((unsigned)nb, (unsigned)((ch + 63) / 64)), dim3(256), 0, st, a, (const float*)nullptr,
+                           rows, ch, (const float*)nullptr, (const float*)nullptr, L.partial);
+        SAPCU_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(col_final_kernel, dim3((unsigned)((ch + 63) / 64)), dim3(256), 0, st, L.partial, nb, ch, L.sums);
+    SAPCU_CHECK_LAUNCH();
+    *sums_out = L.sums;
+    return SAPCU_OK;
+}
+
 }  // namespace sapcu
 
 using namespace sapcu;

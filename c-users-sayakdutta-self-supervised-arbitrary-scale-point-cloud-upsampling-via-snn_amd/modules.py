@@ -427,3 +427,49 @@ class EnhancedSNNDistanceEstimation(_HipModel):
     def reset_states(self):
         """Reference: clears the encoder's state manager (fd/snn_coder.py:889-893), whose 'final' entry is
         created zero and never updated — a functional no-op kept for signature compatibility."""
+
+
+class TrainableSNNDistanceEstimation(EnhancedSNNDistanceEstimation):
+    """``EnhancedSNNDistanceEstimation`` with a training path (row f-5, sapcu_amd/fd_train.py).  Same constructor, same
+    ``state_dict`` keys, shapes and order.  ``eval()``: the inherited HIP engine (the packed blob follows the parameters' version
+    counters, so it is rebuilt after an optimiser step).  ``train()``: ``forward`` is ``fd_train.fd_train_forward`` — hard spikes,
+    batch statistics, dropout, autograd through the HIP training ops; there is no CPU path.  The base class stays inference-only.
+
+    Not built (refused or absent, never emulated): bf16 / GradScaler, HIP-graph capture of the step, ``use_snn_decoder=True``,
+    DataParallel, gradient accumulation."""
+
+    def __init__(self, k=20, emb_dims=512, time_steps_enc=5, time_steps_dec=8, num_heads=4, dropout=0.1, use_snn_decoder=False,
+                 k_scales=[10, 20, 40]):
+        super().__init__(k=k, emb_dims=emb_dims, time_steps_enc=time_steps_enc, time_steps_dec=time_steps_dec, num_heads=num_heads,
+                         dropout=dropout, use_snn_decoder=use_snn_decoder, k_scales=k_scales)
+        self.dropout = float(dropout)
+        self.dropout_generator = None          # a torch.Generator on the model's device makes the dropout masks reproducible
+
+    def train(self, mode=True):
+        return nn.Module.train(self, mode)
+
+    def forward(self, Xc_rotated, taps=None, knn_force=None, force_spikes=None):
+        """eval(): as the base class.  train(): [B,M,3] -> [B]; [B,N,M,3] -> [B,N] with autograd; ``knn_force``: optional tables
+        [T, 3, B, M, min(k, M)]; ``taps`` / ``force_spikes``: the hooks of fd_train.fd_train_forward."""
+        if not self.training:
+            return super().forward(Xc_rotated, taps, knn_force)
+        from . import fd_train
+        if Xc_rotated.dim() == 4:
+            B, N, M, _ = Xc_rotated.shape
+            return self.forward(Xc_rotated.reshape(B * N, M, 3), taps, knn_force, force_spikes).view(B, N)
+        x = self._as_patches(Xc_rotated)
+        self._device()
+        if not x.is_cuda:
+            raise RuntimeError("sapcu_amd models run on a ROCm GPU only (the input is on %s); there is no CPU path" % x.device)
+        p = dict(self.named_parameters())
+        p.update(dict(self.named_buffers()))
+        return fd_train.fd_train_forward(p, x, self.k, tuple(self.k_scales), self.time_steps_enc, self.num_heads, knn=knn_force,
+                                         momentum=0.1, dropout=self.dropout, generator=self.dropout_generator, taps=taps,
+                                         force_spikes=force_spikes)
+
+    def compute_loss(self, pred_distances, gt_distances, reduction='mean', beta=0.1):
+        """fd/snn_coder.py:873-887: smooth-L1 -> (loss, {'total_loss', 'distance_loss'})."""
+        from . import fd_train
+        loss = fd_train.distance_loss(pred_distances, gt_distances, reduction=reduction, beta=beta)
+        value = loss.item() if loss.numel() == 1 else loss
+        return loss, {'total_loss': value, 'distance_loss': value}
