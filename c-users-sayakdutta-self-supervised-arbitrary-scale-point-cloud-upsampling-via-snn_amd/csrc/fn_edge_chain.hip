@@ -338,8 +338,20 @@ __device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float 
 // threads = 64 x (d / 32 / CB).  d = 128: three 256-thread workgroups per CU (51 KiB of LDS each, <= 170 registers per wave).
 // O32: the q|k|v tensor is smaller than 4 GiB — the gathers address it as a scalar base + a 32-bit byte offset per lane (one add
 // per gathered element; the 64-bit form spends a 64-bit multiply-add and two adds on each).
-template <int D, int KK, bool O32>
-__global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB128 : 1)) void fn_edge_chain_kernel(const ChainArgs a) {
+// FILL (d = 512, kk = 12 only; section "filled groups" below): lane group 3's four spare slots, which otherwise replay the group's first
+// edge row, carry four edge rows of a sixteenth point.
+//
+// Filled groups.  64 rows hold five points of 12 and leave four slots idle, 1/16 of everything a group does.  Three groups have 48 spare
+// slots = four points, of which the plain grouping uses three: the filled form takes the points in SUPER-GROUPS of 16 — group 3 sg + p
+// (p = 0..2) runs points 16 sg + 5 p + 0..4 in the slots of a plain group and neighbours 4 p + e of the STRADDLER, point 16 sg + 15, in lane group
+// 3's spare slots (rs = 3, e = 0..3) — so 16 points cost three groups instead of 3.2; the P % 16 points left over run in plain groups of
+// five behind the super-groups.  A straddler's rows go through the chain like any other row (their own edge records in phase 0, the
+// straddler's q_i in the GEMM-1 epilogue) but its 12 rows end in three workgroups: lane group 3 stores their scaled logits and
+// t = v_j + pe to two scratch tensors [P / 16][12][d], and fn_chain_straddler_kernel, launched behind this kernel on the same stream,
+// runs the same chain_softmax_agg over them.  Same products, same order, same softmax routine: the bits of the plain grouping.
+template <int D, int KK, bool O32, bool FILL>
+__device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
+    static_assert(!FILL || (D == 512 && KK == 12), "filled groups: d = 512, kk = 12");
     using S = ChainShape<D>;
     using M = ChainSlots<D, KK>;
     constexpr int CH_ROWS = S::ROWS, RS = S::RS, CS = S::CS, CH_PLANE = S::PLANE, CH_KSTEP = S::KSTEP;
@@ -372,7 +384,8 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
 
     // group of this workgroup: contiguous ranges of groups per XCD (blockIdx & 7), so that the tiles of one patch — which
     // gather the same q / k / v rows — share an L2
-    const int64_t ngroups = (a.P + PPG - 1) / PPG;
+    const int64_t nsuper = FILL ? a.P / 16 : 0;            // super-groups of 16 points = three groups each, then the plain tail groups
+    const int64_t ngroups = 3 * nsuper + (a.P - 16 * nsuper + PPG - 1) / PPG;
     int64_t grp;
     {
         const int64_t nx = gridDim.x < 8 ? 1 : 8;
@@ -381,7 +394,18 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
         grp = x * qd + (x < rem ? x : rem) + slot;
         if (slot >= qd + (x < rem ? 1 : 0)) return;
     }
-    const int64_t pt0 = grp * PPG;
+    int64_t pt0 = grp * PPG, strad = -1;                   // strad: the straddler whose neighbours 4 spos + e ride in lane group 3's spare slots
+    int spos = 0;
+    if (FILL) {
+        if (grp < 3 * nsuper) {
+            const unsigned sgi = (unsigned)grp / 3u;
+            spos = (int)((unsigned)grp - 3u * sgi);
+            pt0 = 16 * (int64_t)sgi + PPG * spos;
+            strad = 16 * (int64_t)sgi + 15;
+        } else {
+            pt0 = 16 * nsuper + (grp - 3 * nsuper) * PPG;
+        }
+    }
     const int npts = (int)((a.P - pt0) < PPG ? (a.P - pt0) : PPG);
 
     f32x4 acc[RS][CS], pe[RS][CS];
@@ -399,7 +423,8 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
             jj = u % KK;
         }
         const bool ok = p < npts;                                            // unused slots replay the group's first edge row
-        const int64_t er = ok ? (pt0 + p) * KK + jj : pt0 * KK;
+        int64_t er = ok ? (pt0 + p) * KK + jj : pt0 * KK;
+        if (FILL && p >= PPG && strad >= 0) er = strad * KK + 4 * spos + jj;      // (p >= PPG: lane group 3's spare slots, jj = e)
         const int2 t2 = a.tab[er];
         if (O32) reinterpret_cast<unsigned*>(rinfo)[tid] = (unsigned)t2.y * (unsigned)(a.ldq * 4);      // byte offset of the neighbour's row
         else rinfo[tid] = t2;
@@ -458,13 +483,14 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
         }
     };
     // q_i (fn:368) of this lane's column: of lane group g's own point, and of the points that live in the spare slots
-    auto load_q = [&](int j, float& qa, float (&qu)[NUA > 0 ? NUA : 1]) {
+    auto load_q = [&](int j, float& qa, float (&qu)[NUA > 0 ? NUA : 1], float& qs) {
         qa = __builtin_nontemporal_load(&a.qkv[(pt0 + (L.g < npts ? L.g : 0)) * a.ldq + L.col[j]]);
+        if (FILL) qs = __builtin_nontemporal_load(&a.qkv[(strad >= 0 ? strad : pt0) * a.ldq + L.col[j]]);
 #pragma unroll
         for (int n = 0; n < NUA; ++n) qu[n] = __builtin_nontemporal_load(&a.qkv[(pt0 + (4 + n < npts ? 4 + n : 0)) * a.ldq + L.col[j]]);
     };
-    float qa[2], qu[2][NUA > 0 ? NUA : 1];
-    load_q(0, qa[0], qu[0]);
+    float qa[2], qu[2][NUA > 0 ? NUA : 1], qs[2] = {0.f, 0.f};
+    load_q(0, qa[0], qu[0], qs[0]);
     gather_kv(0, 0, kq[0], vq[0]);                         // in flight during GEMM 1
     chain_w_prefetch<D>(wp1, cs0, lane, W);
     lds_barrier();                                         // pe1 panel complete
@@ -480,7 +506,7 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
         for (int j = 0; j < CS; ++j) {
             const float b1 = a.b1[L.col[j]];
             const NeuronP n1 = chain_lif(a.lif1, D, L.col[j]);
-            if (j + 1 < CS) load_q(j + 1, qa[(j + 1) & 1], qu[(j + 1) & 1]);
+            if (j + 1 < CS) load_q(j + 1, qa[(j + 1) & 1], qu[(j + 1) & 1], qs[(j + 1) & 1]);
 #pragma unroll
             for (int up = 0; up < NUP; ++up) {
                 const int u = j * NUP + up;
@@ -505,7 +531,8 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
 #pragma unroll
                         for (int sg = 0; sg < 4; ++sg) {
                             const int p = M::point(rs, sg, e);
-                            c[sg] = p >= 4 ? qu[j & 1][p - 4 < NUA ? p - 4 : 0] : qa[j & 1];       // (unused slots: any value)
+                            // (unused slots: any value; FILL: the straddler's)
+                            c[sg] = p >= 4 ? qu[j & 1][p - 4 < NUA ? p - 4 : 0] : (FILL && p < 0 ? qs[j & 1] : qa[j & 1]);
                         }
                         qv = group_select(c[0], c[1], c[2], c[3], g0, g1);
                     }
@@ -558,6 +585,17 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
                 const f32x2 hi = pk_fma(f32x2{acc[i][j][2], acc[i][j][3]}, k16, b32) * is2;
                 acc[i][j] = f32x4{lo.x, lo.y, hi.x, hi.y};
             }
+            // the straddler's four rows: logits and t leave for fn_chain_straddler_kernel (streamed out once, like the result rows)
+            if (FILL) {
+                if (L.g == 3 && strad >= 0) {
+                    const int64_t o = ((strad >> 4) * KK + 4 * spos) * D + L.col[j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        __builtin_nontemporal_store(acc[RS - 1][j][e], &a.fill_x[o + e * D]);
+                        __builtin_nontemporal_store(pe[RS - 1][j][e], &a.fill_t[o + e * D]);
+                    }
+                }
+            }
             // lane group g's own point: its kk rows are this lane's registers, in neighbour order
             {
                 float xs[KK], ts[KK];
@@ -601,6 +639,38 @@ __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB1
 }
 
 template <int D, int KK, bool O32>
+__global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB128 : 1)) void fn_edge_chain_kernel(const ChainArgs a) {
+    fn_edge_chain_body<D, KK, O32, false>(a);
+}
+
+// d = 512, kk = 12 with filled groups (a.fill_x / a.fill_t)
+template <bool O32>
+__global__ __launch_bounds__(ChainShape<512>::NW * 64, 1) void fn_edge_chain_fill_kernel(const ChainArgs a) {
+    fn_edge_chain_body<512, 12, O32, true>(a);
+}
+
+// The straddlers of the filled groups: one thread per (straddler, column) reads its 12 scaled logits and 12 t = v_j + pe in neighbour
+// order from the scratch the three groups of its super-group wrote and runs the chain kernel's own softmax-aggregate.
+template <int KK>
+__global__ __launch_bounds__(256) void fn_chain_straddler_kernel(const float* __restrict__ fx, const float* __restrict__ ft, int64_t nsuper,
+                                                                 int d, float* __restrict__ res, int res_split) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nsuper * d) return;
+    const int64_t sgi = t / d;
+    const int col = (int)(t - sgi * d);
+    float xs[KK], ts[KK];
+#pragma unroll
+    for (int jj = 0; jj < KK; ++jj) {
+        xs[jj] = __builtin_nontemporal_load(&fx[(sgi * KK + jj) * d + col]);
+        ts[jj] = __builtin_nontemporal_load(&ft[(sgi * KK + jj) * d + col]);
+    }
+    const float out = chain_softmax_agg<KK>(xs, ts);
+    const int64_t pt = 16 * sgi + 15;
+    if (res_split) chain_store_split_nt(res, pt, d, col, out);
+    else __builtin_nontemporal_store(out, &res[pt * d + col]);
+}
+
+template <int D, int KK, bool O32>
 static int launch_chain_t(const ChainArgs& a, hipStream_t st) {
     constexpr int lds = ChainShape<D>::LDS;
     static DeviceOnce lds_once;                         // one per kernel instantiation, one bit per device
@@ -610,6 +680,23 @@ static int launch_chain_t(const ChainArgs& a, hipStream_t st) {
     const int64_t grid = ngroups < 8 ? ngroups : ((ngroups + 7) / 8) * 8;      // 8 XCD ranges of equal slot count
     SAPCU_CHECK_ARG(grid < 0x7fffffffLL, "edge_chain: too many groups");
     hipLaunchKernelGGL((fn_edge_chain_kernel<D, KK, O32>), dim3((unsigned)grid), dim3(ChainShape<D>::NW * 64), lds, st, a);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+template <bool O32>
+static int launch_chain_fill_t(const ChainArgs& a, hipStream_t st) {
+    constexpr int lds = ChainShape<512>::LDS, PPG = ChainSlots<512, 12>::PPG;
+    static DeviceOnce lds_once;
+    SAPCU_SET_MAX_LDS(lds_once, (&fn_edge_chain_fill_kernel<O32>), lds);
+    const int64_t nsuper = a.P / 16;
+    const int64_t ngroups = 3 * nsuper + (a.P - 16 * nsuper + PPG - 1) / PPG;
+    const int64_t grid = ngroups < 8 ? ngroups : ((ngroups + 7) / 8) * 8;
+    SAPCU_CHECK_ARG(grid < 0x7fffffffLL, "edge_chain: too many groups");
+    hipLaunchKernelGGL((fn_edge_chain_fill_kernel<O32>), dim3((unsigned)grid), dim3(ChainShape<512>::NW * 64), lds, st, a);
+    SAPCU_CHECK_LAUNCH();
+    hipLaunchKernelGGL((fn_chain_straddler_kernel<12>), dim3((unsigned)((nsuper * 512 + 255) / 256)), dim3(256), 0, st, a.fill_x, a.fill_t,
+                       nsuper, 512, a.res, a.res_split);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
 }
@@ -630,6 +717,8 @@ int launch_fn_edge_chain(ChainArgs a, const float* patch, const int32_t* idx, in
     const bool o32 = !a.wide_offsets && (uint64_t)a.P * (uint64_t)a.ldq * 4u + 3u * (uint64_t)d * 4u < (1ull << 32) && a.ldq > 0;
     if (d == 128) return o32 ? launch_chain_t<128, 24, true>(a, st) : launch_chain_t<128, 24, false>(a, st);
     if (d == 256) return o32 ? launch_chain_t<256, 18, true>(a, st) : launch_chain_t<256, 18, false>(a, st);
+    // filled groups: the caller gave the two scratch areas ([P / 16][12][512] floats each) and there is at least one super-group
+    if (a.fill_x && a.fill_t && a.P >= 16) return o32 ? launch_chain_fill_t<true>(a, st) : launch_chain_fill_t<false>(a, st);
     return o32 ? launch_chain_t<512, 12, true>(a, st) : launch_chain_t<512, 12, false>(a, st);
 }
 

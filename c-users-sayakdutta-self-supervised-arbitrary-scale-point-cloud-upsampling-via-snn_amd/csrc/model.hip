@@ -99,6 +99,7 @@ struct sapcu_model {
     bool opt_bt = true;               // SAPCU_BT=0: split-row GEMMs on the ring kernel only
     bool opt_chain = true;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
     bool opt_chain_wide = false;      // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
+    bool opt_chain_fill = true;       // SAPCU_CHAIN_FILL=0: the d = 512 fused chain in plain groups of five points, four slots of 64 idle
     bool opt_fn_maxfuse = true;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
     bool opt_fn_fold_out = true;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
     bool opt_fd_maxfuse = true;       // SAPCU_FD_MAXFUSE=0: multi_scale_conv GEMM + rowgroup_max
@@ -165,6 +166,7 @@ static void read_env_switches(sapcu_model* m) {
     m->opt_bt = !env_is("SAPCU_BT", "0");
     m->opt_chain = !env_is("SAPCU_CHAIN", "0");
     m->opt_chain_wide = env_is("SAPCU_CHAIN", "wide");
+    m->opt_chain_fill = !env_is("SAPCU_CHAIN_FILL", "0");
     m->opt_fn_maxfuse = !env_is("SAPCU_FN_MAXFUSE", "0");
     m->opt_fn_fold_out = !env_is("SAPCU_FN_FOLD_OUT", "0");
     m->opt_fd_maxfuse = !env_is("SAPCU_FD_MAXFUSE", "0");
@@ -352,6 +354,7 @@ struct FnEdge {
     int64_t P;
     int mp, l, d, kk, sb, SP;
     float sqrt_hd;
+    int64_t b1_floats;       // size of W.B1 (FnPlan::edge_floats)
 };
 
 // the whole edge chain in one kernel, activations in LDS (fn_edge_chain.hip)      fn:355-389
@@ -367,6 +370,16 @@ static int fn_edge_chain_fused(const sapcu_model* m, const FnWs& W, const FnEdge
     ca.w3p = cw + chain_w_off(e.l, 2); ca.b3 = m->p(sb + B_GAMMA2_B);
     ca.inv_sqrt_hd = 1.0f / e.sqrt_hd;
     ca.res = W.RES; ca.res_split = e.SP; ca.T = 4; ca.wide_offsets = m->opt_chain_wide ? 1 : 0;
+    // d = 512, filled groups: the straddlers' logits go to W.X (consumed by the q|k|v GEMM, not written again before the chain has
+    // run) and their t = v_j + pe to W.B1 (unused between the last unfused chain and conv_final) — where both hold
+    // [P / 16][12][512] floats; else the plain grouping
+    if (m->opt_chain_fill && d == 512 && e.kk == 12) {
+        const int64_t need = (e.P / 16) * 12 * 512;
+        if (need > 0 && need <= e.P * 512 && need <= e.b1_floats) {
+            ca.fill_x = W.X;
+            ca.fill_t = W.B1;
+        }
+    }
     return launch_fn_edge_chain(ca, e.pc, W.idx[e.l], d, e.kk, W.tab, W.pdiff, st);
 }
 
@@ -449,7 +462,7 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
             // q|k|v = LIF(w_qs|w_ks|w_vs (x))                                       fn:322-335
             SAPCU_TRY(gemm(m, W.X, P, d, d, m->p(sb + B_QKV_W), 3 * d, m->p(sb + B_QKV_B), W.QKV, 3 * d, EPI_LIF, st,
                            m->p(sb + B_QKV_LIF), 4, nullptr, 0, SP));
-            const FnEdge e{pc, P, mp, l, d, pl.kk[l], sb, SP, (float)sqrt((double)(d / m->heads))};
+            const FnEdge e{pc, P, mp, l, d, pl.kk[l], sb, SP, (float)sqrt((double)(d / m->heads)), pl.edge_floats};
             SAPCU_TRY(fn_block_fused(m, l, mp) ? fn_edge_chain_fused(m, W, e, st) : fn_edge_chain_unfused(m, W, e, st));
             // out_proj, fc2 + residual                                              fn:393-394
             if (m->opt_fn_fold_out) {
