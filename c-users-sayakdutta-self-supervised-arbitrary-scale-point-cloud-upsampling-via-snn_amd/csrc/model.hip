@@ -100,6 +100,7 @@ struct sapcu_model {
     bool opt_chain = true;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
     bool opt_chain_wide = false;      // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
     bool opt_chain_fill = true;       // SAPCU_CHAIN_FILL=0: the d = 512 fused chain in plain groups of five points, four slots of 64 idle
+    bool opt_shortk = true;           // SAPCU_SHORTK=0: fc1 / conv_final on gemm_sf16_kernel instead of gemm_shortk.hip
     bool opt_fn_maxfuse = true;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
     bool opt_fn_fold_out = true;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
     bool opt_fd_maxfuse = true;       // SAPCU_FD_MAXFUSE=0: multi_scale_conv GEMM + rowgroup_max
@@ -167,6 +168,7 @@ static void read_env_switches(sapcu_model* m) {
     m->opt_chain = !env_is("SAPCU_CHAIN", "0");
     m->opt_chain_wide = env_is("SAPCU_CHAIN", "wide");
     m->opt_chain_fill = !env_is("SAPCU_CHAIN_FILL", "0");
+    m->opt_shortk = !env_is("SAPCU_SHORTK", "0");
     m->opt_fn_maxfuse = !env_is("SAPCU_FN_MAXFUSE", "0");
     m->opt_fn_fold_out = !env_is("SAPCU_FN_FOLD_OUT", "0");
     m->opt_fd_maxfuse = !env_is("SAPCU_FD_MAXFUSE", "0");
@@ -201,6 +203,11 @@ static int run_gemm(const sapcu_model* m, GemmArgs& g, hipStream_t st) {
         g.w16_lo = (const _Float16*)m->w16_lo + off;
         g.ovf = m->ovf_dev;
         if (g.a_split) return launch_gemm_split_rows(g, st, m->opt_bt);   // A already split by its producer: all-DMA kernels
+        if (m->opt_shortk && gemm_shortk_ok(g)) return launch_gemm_shortk(g, st);   // short K, neuron epilogue: every wave does both
+        if (g.max_out) {
+            set_error("run_gemm: a direct max output needs the short-K kernel");
+            return SAPCU_ERR_ARG;
+        }
         if (g.k % 64 == 0) return launch_gemm_sf16(g, st);
     }
     if (g.a_split || g.c_split || g.c2_split) {
@@ -491,9 +498,12 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
             g.a = W.cat; g.r = P; g.k = 192; g.lda = 192; g.w = m->p(FN_FINAL_W); g.n = m->emb; g.bias = m->p(FN_FINAL_B);
             g.ldc = m->emb; g.epi = EPI_LIF_MAX; g.lif = m->p(FN_FINAL_LIF); g.lif_T = m->T;
             g.max_keys = reinterpret_cast<unsigned*>(W.B1); g.max_m = mp;
-            SAPCU_CHECK_HIP(hipMemsetAsync(g.max_keys, 0, (size_t)cb * m->emb * 4, st));
+            // whole patches per row group (M = 48): gemm_shortk.hip takes the max in registers and writes pooled itself
+            const bool direct = m->opt_shortk && mp == 48;
+            if (direct) g.max_out = W.pooled;
+            else SAPCU_CHECK_HIP(hipMemsetAsync(g.max_keys, 0, (size_t)cb * m->emb * 4, st));
             SAPCU_TRY(run_gemm(m, g, st));
-            SAPCU_TRY(launch_decode_max_keys(g.max_keys, cb * m->emb, W.pooled, st));
+            if (!direct) SAPCU_TRY(launch_decode_max_keys(g.max_keys, cb * m->emb, W.pooled, st));
         } else {
             SAPCU_TRY(gemm(m, W.cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), W.B1, m->emb, EPI_LIF, st,
                            m->p(FN_FINAL_LIF), m->T));
@@ -920,7 +930,9 @@ int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, in
     if (w16_ws && (g.a_split || k % 64 == 0)) {   // f32-A split-f16 kernel steps k by 64; other depths run on exact f32
         SAPCU_TRY(split_into_ws(w, (int64_t)n * k, w16_ws, g, (hipStream_t)stream));
         // a_split_rows = 2: the ring kernel even where the big-tile kernel takes the shape (bit-identical; parity tests)
-        return g.a_split ? launch_gemm_split_rows(g, (hipStream_t)stream, a_split_rows != 2) : launch_gemm_sf16(g, (hipStream_t)stream);
+        if (g.a_split) return launch_gemm_split_rows(g, (hipStream_t)stream, a_split_rows != 2);
+        if (!env_is("SAPCU_SHORTK", "0") && gemm_shortk_ok(g)) return launch_gemm_shortk(g, (hipStream_t)stream);
+        return launch_gemm_sf16(g, (hipStream_t)stream);
     }
     SAPCU_CHECK_ARG(!g.c_split, "gemm: split-row output needs k %% 64 == 0 on the f32-A path");
     return launch_gemm(g, (hipStream_t)stream);

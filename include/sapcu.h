@@ -275,7 +275,9 @@ int sapcu_patch_knn(const float* feat, int64_t b, int m, int c, int ld, int k, i
  * A handle is immutable after creation: the environment switches (SAPCU_GEMM=f32, SAPCU_CHUNK, SAPCU_WS_BUDGET_MB and the
  * parity / ablation switches SAPCU_BT, SAPCU_CHAIN (= 0, or "wide"), SAPCU_FN_MAXFUSE, SAPCU_FD_MAXFUSE, SAPCU_FD_SPLIT, SAPCU_FD_FUSED = 0, and
  * SAPCU_FN_FOLD_OUT = 0: fn blocks end with out_proj and fc2 as two GEMMs instead of the one folded at create, results equal to rounding;
- * SAPCU_CHAIN_FILL = 0: fn block 3's fused edge chain in plain groups of five points instead of super-groups of 16, bit-identical) are
+ * SAPCU_CHAIN_FILL = 0: fn block 3's fused edge chain in plain groups of five points instead of super-groups of 16, bit-identical;
+ * SAPCU_SHORTK = 0: fn's fc1 and conv_final layers on the general f32-A split-f16 kernel instead of the short-K one, bit-identical —
+ * sapcu_gemm_f32, which has no handle, reads this one switch at each call) are
  * read HERE, once; a forward never reads the environment.  Forwards of one handle (or of several) may run concurrently on
  * different streams / host threads as long as each has its own workspace; launch attributes are set once per device. */
 int sapcu_model_create(int kind, const int32_t* hparams_host, int n_hparams, const float* blob,
