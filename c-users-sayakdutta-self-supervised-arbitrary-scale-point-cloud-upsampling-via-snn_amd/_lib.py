@@ -112,6 +112,17 @@ _FD_TRAIN_SIGNATURES = {
 }
 FD_TRAIN_EXPORTS = tuple(_FD_TRAIN_SIGNATURES)
 
+# include/sapcu_fd_edgeconv.h: the factored EdgeConv training op of fd's blocks 1-3 (a fourth table)
+_FD_EDGECONV_SIGNATURES = {
+    "sapcu_fd_edgeconv_stats_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "sapcu_fd_edgeconv_stats": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 4 + [c_void_p, c_int64, c_void_p]),
+    "sapcu_fd_edgeconv_max_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "sapcu_fd_edgeconv_backward_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "sapcu_fd_edgeconv_backward": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p] * 4 +
+                                   [c_void_p, c_int64, c_void_p]),
+}
+FD_EDGECONV_EXPORTS = tuple(_FD_EDGECONV_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -134,7 +145,7 @@ def load(path=None):
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
-            list(_INTERNAL_SIGNATURES.items()):
+            list(_FD_EDGECONV_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

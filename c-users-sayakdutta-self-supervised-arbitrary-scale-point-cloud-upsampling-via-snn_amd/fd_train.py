@@ -14,8 +14,12 @@ Two facts of the reference shape this module:
   therefore not be compared with a reference run: parity is teacher-forced on the reference's own tables (``knn=``) and spikes
   (``force_spikes=``).
 
-Not built, and refused where a caller could ask for it: bf16 / GradScaler, HIP-graph capture of the step, ``use_snn_decoder=True``,
-DataParallel, gradient accumulation.  The decoder works on [P, <= 256] tensors: its Linear / BatchNorm layers are the HIP ops of
+bf16: every GEMM / weight gradient here goes through ``train._gemm`` / ``_wgrad`` and so follows ``train.gemm_precision``;
+``edgeconv_form("factored")`` runs blocks 1-3 through ``edgeconv_factored`` (include/sapcu_fd_edgeconv.h, csrc/fd_edgeconv_ops.hip),
+which never builds the [P M kk, 2C] edge tensors.  ``fd_trainer.AmpTrainer`` drives both, a GradScaler and gradient accumulation.
+
+Not built, and refused where a caller could ask for it: HIP-graph capture of the step, ``use_snn_decoder=True``, DataParallel.
+The decoder works on [P, <= 256] tensors: its Linear / BatchNorm layers are the HIP ops of
 train.py, GELU, LayerNorm, the softmax over heads, Softplus, the loss and the dropout masks are torch ops, as in fn's training.
 """
 import torch
@@ -257,6 +261,135 @@ def conv_bn_lrelu_max(x, weight, gamma, beta, group=1, idx=None, eps=1e-5, runni
     return _ConvBnLreluMax.apply(x, idx, weight, gamma, beta, group, eps, running, reps)
 
 
+# How blocks 1-3 of fd_train_forward evaluate their EdgeConv: "feature" = conv_bn_lrelu_max(idx=...) — the [P M kk, 2C] graph
+# feature is built, forward and backward; "factored" = edgeconv_factored — one point-level GEMM and gathers (the parity reference
+# stays "feature"; fd_trainer.AmpTrainer selects the form).  Block 0's xyz EdgeConvs (C = 3) are on the feature path in both:
+# x_n - x_i cancels and must be formed in f32 before any rounding.
+_EDGECONV_FORM = ["feature"]
+
+
+class edgeconv_form(object):
+    """``with edgeconv_form("factored"): loss = ...; loss.backward()`` — in the style of ``train.gemm_precision``.  The form is read
+    in the forward; the backward of an op is the backward of the form its forward ran in."""
+
+    def __init__(self, form):
+        if form not in ("feature", "factored"):
+            raise ValueError("edgeconv_form: 'feature' or 'factored'")
+        self.form = form
+
+    def __enter__(self):
+        self.prev = _EDGECONV_FORM[0]
+        _EDGECONV_FORM[0] = self.form
+        return self
+
+    def __exit__(self, *exc):
+        _EDGECONV_FORM[0] = self.prev
+        return False
+
+
+def _count_bad(bad):
+    acc = _BAD.get(bad.device)
+    if acc is None:
+        acc = _BAD[bad.device] = torch.zeros((1,), dtype=torch.int32, device=bad.device)
+    acc.add_(bad)
+
+
+def _edgeconv_factored_forward(lib, x, wst, idx, ga, be, eps):
+    """x [P*M, C], wst = [W1 ; W2] [2 cout, C], idx int32 [P, M, kk] -> ab = [x W1^T | x W2^T], mean, var, invstd, out, arg.
+    The caller holds torch.cuda.device(x.device)."""
+    P, M, kk = idx.shape
+    cout, dev = wst.shape[0] // 2, x.device
+    ab = torch.empty((P * M, 2 * cout), dtype=torch.float32, device=dev)
+    T._gemm(lib, x, wst, None, ab)
+    mean, var, invstd = (torch.empty((cout,), dtype=torch.float32, device=dev) for _ in range(3))
+    nbytes = int(lib.sapcu_fd_edgeconv_stats_workspace_bytes(P, M, kk, cout))
+    ws = torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)
+    st = _lib.current_stream()
+    _lib.check(lib.sapcu_fd_edgeconv_stats(_lib.ptr(ab), _lib.ptr(idx), P, M, kk, cout, float(eps), _lib.ptr(mean), _lib.ptr(var),
+                                           _lib.ptr(invstd), None, _lib.ptr(ws), nbytes, st))
+    out = torch.empty((P * M, cout), dtype=torch.float32, device=dev)
+    arg = torch.empty((P * M, cout), dtype=torch.int32, device=dev)
+    _lib.check(lib.sapcu_fd_edgeconv_max_forward(_lib.ptr(ab), _lib.ptr(idx), P, M, kk, cout, _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(ga),
+                                                 _lib.ptr(be), _lib.ptr(out), _lib.ptr(arg), st))
+    return ab, mean, var, invstd, out, arg
+
+
+def _edgeconv_factored_backward(lib, x, wst, idx, ga, be, ab, mean, invstd, arg, g, need_dx=True):
+    """-> dx [P*M, C] | None, dwst [2 cout, C], dgamma, dbeta: the three HIP passes of sapcu_fd_edgeconv_backward, then ONE
+    point-level weight gradient and ONE point-level GEMM.  The caller holds torch.cuda.device(x.device)."""
+    P, M, kk = idx.shape
+    rows, cin = x.shape
+    cout, dev = wst.shape[0] // 2, x.device
+    gab = torch.empty_like(ab)
+    dgamma, dbeta = torch.empty_like(ga), torch.empty_like(be)
+    bad = torch.empty((1,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.sapcu_fd_edgeconv_backward_workspace_bytes(P, M, kk, cout))
+    ws = torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)
+    st = _lib.current_stream()
+    _lib.check(lib.sapcu_fd_edgeconv_backward(_lib.ptr(ab), _lib.ptr(idx), _lib.ptr(g), _lib.ptr(arg), P, M, kk, cout, _lib.ptr(mean),
+                                              _lib.ptr(invstd), _lib.ptr(ga), _lib.ptr(be), _lib.ptr(gab), _lib.ptr(dgamma), _lib.ptr(dbeta),
+                                              _lib.ptr(bad), _lib.ptr(ws), nbytes, st))
+    _count_bad(bad)
+    dwst = torch.empty_like(wst)
+    tws, tbytes = T._ws(lib, rows, 2 * cout, cin, dev)
+    T._wgrad(lib, gab, x, rows, 2 * cout, cin, dwst, None, tws, tbytes, st)
+    dx = None
+    if need_dx:
+        dx = torch.empty_like(x)
+        T._gemm(lib, gab, wst.t().contiguous(), None, dx)            # dx[r, c] = gab[r, n] . (Wst^T)[c, n]^T
+    return dx, dwst, dgamma, dbeta
+
+
+class _EdgeConvFactored(torch.autograd.Function):
+    """The job of _ConvBnLreluMax with idx, without the edge tensors: y[i, j] = s[n(i, j)] - a[i] with [a | b] = x [W1 ; W2]^T and
+    s = a + b (include/sapcu_fd_edgeconv.h).  Saved for the backward: x, the stacked weight and ab [P*M, 2 cout]."""
+
+    @staticmethod
+    def forward(ctx, x, idx, weight, gamma, beta, eps, running, reps):
+        _need_cuda(x, "edgeconv_factored")
+        lib = _lib.load()
+        P, M, kk = idx.shape
+        _check_patch_shape(M, kk)
+        x = x.contiguous()
+        rows, C = x.shape
+        w = weight.detach().reshape(weight.shape[0], -1)
+        cout = w.shape[0]
+        if rows != P * M or w.shape[1] != 2 * C:
+            raise ValueError("edgeconv_factored: x [%d, %d], idx %s and weight %s do not fit" % (rows, C, tuple(idx.shape), tuple(weight.shape)))
+        if C % 32 or cout % 32:
+            raise ValueError("edgeconv_factored: channel counts must be multiples of 32 (got %d -> %d)" % (C, cout))
+        if rows * kk < 2:
+            raise ValueError("BatchNorm in training mode needs more than 1 value per channel (got %d rows)" % (rows * kk))
+        wst = torch.cat([w[:, :C], w[:, C:]], dim=0).contiguous()         # W1 and W2 are rounded (bf16 mode) separately
+        idx = idx.to(torch.int32).contiguous()
+        ga, be = gamma.detach().contiguous(), beta.detach().contiguous()
+        with torch.cuda.device(x.device):
+            ab, mean, var, invstd, out, arg = _edgeconv_factored_forward(lib, x, wst, idx, ga, be, eps)
+        _update_running(running, mean, var, rows * kk, int(reps))
+        ctx.save_for_backward(x, wst, ga, be, ab, mean, invstd, arg)
+        ctx.idx, ctx.wshape = idx, weight.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, wst, ga, be, ab, mean, invstd, arg = ctx.saved_tensors
+        cout = wst.shape[0] // 2
+        with torch.cuda.device(x.device):
+            dx, dwst, dgamma, dbeta = _edgeconv_factored_backward(lib, x, wst, ctx.idx, ga, be, ab, mean, invstd, arg, g.contiguous(),
+                                                                  ctx.needs_input_grad[0])
+        dw = torch.cat([dwst[:cout], dwst[cout:]], dim=1).reshape(ctx.wshape)
+        return dx, None, dw, dgamma, dbeta, None, None, None
+
+
+def edgeconv_factored(x, weight, gamma, beta, idx, eps=1e-5, running=None, reps=1):
+    """``conv_bn_lrelu_max(x, weight, gamma, beta, group=kk, idx=idx)`` in factored form: x [P*M, C] (C % 32 == 0), idx int32
+    [P, M, kk], weight [c_out, 2C(, 1, 1)] -> [P*M, c_out], with one GEMM on the P*M point rows (it follows train.gemm_precision)
+    and gathers over the neighbours instead of any [P*M*kk, .] tensor, forward or backward.  An index outside [0, M) gives that edge
+    y = 0 and no gradient and is counted for take_bad_index_count()."""
+    return _EdgeConvFactored.apply(x, idx, weight, gamma, beta, eps, running, reps)
+
+
 def feature_knn(x, P, M, k):
     """The library's free-running neighbour rule on features x [P*M, C]: ``sapcu_patch_knn`` — the k highest scores
     -|x_i - x_j|^2 in descending order, equal scores by ascending index -> int32 [P, M, k]."""
@@ -326,6 +459,7 @@ def fd_train_forward(p, patches, k=20, k_scales=(10, 20, 40), time_steps_enc=5, 
         knn = knn.to(device=dev, dtype=torch.int32)
         if int(knn.min()) < 0 or int(knn.max()) >= M:
             raise ValueError("knn holds indices outside [0, %d)" % M)
+    factored = _EDGECONV_FORM[0] == "factored"                     # blocks 1-3 only; block 0 (xyz, C = 3) stays on the feature path
     states = [None] * 4
     pooled = []
     for t in range(Tn):
@@ -336,7 +470,12 @@ def fd_train_forward(p, patches, k=20, k_scales=(10, 20, 40), time_steps_enc=5, 
             if b > 0:
                 idx = knn[t, b - 1] if knn is not None else feature_knn(cur.detach(), P, M, kk)
                 tabs.append(idx)
-                cur = bn("conv_blocks.%d" % (b - 1), kk, cur, idx)
+                if factored:
+                    pre = "conv_blocks.%d" % (b - 1)
+                    cur = edgeconv_factored(cur, enc[pre + ".0.weight"], enc[pre + ".1.weight"], enc[pre + ".1.bias"], idx, eps=eps,
+                                            running=T._running(enc, pre + ".1", momentum))
+                else:
+                    cur = bn("conv_blocks.%d" % (b - 1), kk, cur, idx)
             if taps is not None:
                 th_used = states[b][1] if states[b] is not None else enc["snn_blocks.%d.threshold_base" % b].detach().expand_as(cur)
                 _tap(taps, "threshold", th_used)

@@ -3,8 +3,12 @@
 backward and step, ``fn_trainer.run_epoch(trainer, loader, clamp_parameters=True)`` is the batch loop of the reference's
 trainfd.py:264-313 in f32.  ``SyntheticFdPatches`` stands in for the reference's h5 distance-field data, absent here.
 
-Not built, and the constructor says so: bf16 / GradScaler (``use_amp``), HIP-graph capture of the step, DataParallel
-(``model.module``), gradient accumulation, ``use_snn_decoder=True`` (refused by the model)."""
+``Trainer`` is the f32 step and refuses ``use_amp`` / ``scaler`` / ``gradient_accumulation``; ``AmpTrainer`` is the reference's
+default configuration (config/fd.yaml ``use_amp: true``, trainfd.py:194-291): bf16 GEMMs, an optional GradScaler, gradient
+accumulation, and the EdgeConv form of blocks 1-3.
+
+Not built, and the constructors say so: HIP-graph capture of the step, DataParallel (``model.module``), ``use_snn_decoder=True``
+(refused by the model)."""
 import numpy as np
 import torch
 
@@ -13,9 +17,9 @@ class Trainer:
     def __init__(self, model, optimizer, device=None, input_type='pointcloud', vis_dir=None, threshold=0.5, eval_sample=False,
                  grad_clip=None, grad_clip_type='norm', use_amp=False, scaler=None, gradient_accumulation=1):
         if use_amp or scaler is not None:
-            raise NotImplementedError("fd training runs in f32: bf16 / GradScaler are not built")
+            raise NotImplementedError("fd_trainer.Trainer runs in f32: bf16 / GradScaler are AmpTrainer's")
         if gradient_accumulation != 1:
-            raise NotImplementedError("fd training: gradient accumulation is not built")
+            raise NotImplementedError("fd_trainer.Trainer: gradient accumulation is AmpTrainer's")
         if hasattr(model, 'module'):
             raise NotImplementedError("fd training: DataParallel is not built (one process per GPU)")
         if grad_clip_type not in ('norm', 'value'):
@@ -137,6 +141,79 @@ class Trainer:
         reset = getattr(self.model, 'reset_states', None)
         if reset is not None:
             reset()
+
+
+class AmpTrainer(Trainer):
+    """``Trainer`` with the options of the reference's default fd configuration (trainfd.py:194-291); the step mirrors
+    ``fn_trainer.Trainer.train_step``.  ``use_amp``: the GEMMs, data and weight gradients of the step on bf16 operands with f32
+    accumulation (``train.gemm_precision``; BatchNorm statistics, neurons, softmax, loss and optimiser stay f32, as under autocast;
+    block 0's xyz EdgeConvs form x_n - x_i in f32 first).  ``scaler``: a GradScaler, driven through scale / unscale_ / step / update
+    when ``use_amp`` (bf16 needs no loss scaling; a reference script runs unchanged).  ``gradient_accumulation``: loss / n, clip and
+    step on every n-th call.  ``edgeconv``: how blocks 1-3 run (``fd_train.edgeconv_form``); "factored" is the measured faster of
+    the two in bf16."""
+
+    def __init__(self, model, optimizer, device=None, input_type='pointcloud', vis_dir=None, threshold=0.5, eval_sample=False,
+                 grad_clip=None, grad_clip_type='norm', use_amp=True, scaler=None, gradient_accumulation=1, edgeconv="factored"):
+        super().__init__(model, optimizer, device=device, input_type=input_type, vis_dir=vis_dir, threshold=threshold,
+                         eval_sample=eval_sample, grad_clip=grad_clip, grad_clip_type=grad_clip_type)
+        if edgeconv not in ("feature", "factored"):
+            raise ValueError("edgeconv must be 'feature' or 'factored'")
+        if int(gradient_accumulation) < 1:
+            raise ValueError("gradient_accumulation must be >= 1")
+        self.use_amp, self.scaler, self.gradient_accumulation, self.edgeconv = bool(use_amp), scaler, int(gradient_accumulation), edgeconv
+        self.accumulation_step = 0
+
+    def _abort(self):
+        self.optimizer.zero_grad()
+        self.accumulation_step = 0
+        return None, None
+
+    def train_step(self, data):
+        """-> (loss value, loss dict); (None, None) when the loss or a gradient is not finite (gradients zeroed, the accumulation
+        counter reset); RuntimeError when a neighbour index outside its patch reached an EdgeConv backward."""
+        from . import fd_train
+        from . import train as T
+        self.model.train()
+        if self.accumulation_step == 0:
+            self.optimizer.zero_grad()
+        self.accumulation_step += 1
+        self.reset_model_states()
+        fd_train.take_bad_index_count()
+        amp = self.use_amp and self.scaler is not None
+        with T.gemm_precision("bf16" if self.use_amp else "f32"), fd_train.edgeconv_form(self.edgeconv):     # forward AND backward
+            loss, loss_dict = self.compute_loss_with_dict(data)
+            if not bool(torch.isfinite(loss)):
+                print("WARNING: NaN/Inf in loss value")
+                return self._abort()
+            scaled = loss / self.gradient_accumulation if self.gradient_accumulation != 1 else loss
+            (self.scaler.scale(scaled) if amp else scaled).backward()
+        bad = fd_train.take_bad_index_count()
+        if bad:
+            self._abort()
+            raise RuntimeError("fd training step: %d neighbour indices outside their patch reached the EdgeConv backward" % bad)
+        if self.accumulation_step % self.gradient_accumulation == 0:
+            total = None
+            if amp:
+                self.scaler.unscale_(self.optimizer)
+            if self.grad_clip is not None and self.grad_clip > 0:
+                if self.grad_clip_type == 'norm':
+                    total = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.grad_clip)
+                else:
+                    torch.nn.utils.clip_grad_value_(self.model.parameters(), self.grad_clip)
+            if total is None:
+                grads = [prm.grad for prm in self.model.parameters() if prm.grad is not None]
+                total = torch.stack(torch._foreach_norm(grads)).sum()
+            if not bool(torch.isfinite(total)):
+                print("WARNING: NaN/Inf in gradients")
+                return self._abort()
+            if amp:
+                self.scaler.step(self.optimizer)
+                self.scaler.update()
+            else:
+                self.optimizer.step()
+            self.optimizer.zero_grad()
+            self.accumulation_step = 0
+        return loss.item(), loss_dict
 
 
 def rotation_to_x(normal):

@@ -435,8 +435,10 @@ class TrainableSNNDistanceEstimation(EnhancedSNNDistanceEstimation):
     counters, so it is rebuilt after an optimiser step).  ``train()``: ``forward`` is ``fd_train.fd_train_forward`` — hard spikes,
     batch statistics, dropout, autograd through the HIP training ops; there is no CPU path.  The base class stays inference-only.
 
-    Not built (refused or absent, never emulated): bf16 / GradScaler, HIP-graph capture of the step, ``use_snn_decoder=True``,
-    DataParallel, gradient accumulation."""
+    bf16 GEMM operands, a GradScaler, gradient accumulation and the factored EdgeConv of blocks 1-3 are ``fd_trainer.AmpTrainer``'s
+    (``train.gemm_precision`` / ``fd_train.edgeconv_form`` around forward and backward).
+
+    Not built (refused or absent, never emulated): HIP-graph capture of the step, ``use_snn_decoder=True``, DataParallel."""
 
     def __init__(self, k=20, emb_dims=512, time_steps_enc=5, time_steps_dec=8, num_heads=4, dropout=0.1, use_snn_decoder=False,
                  k_scales=[10, 20, 40]):

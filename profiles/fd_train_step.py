@@ -1,7 +1,9 @@
 """Step time, clouds/s and launch count of one fd training step (row f-5) at the reference's shape — config/fd.yaml: 4 clouds x 16
 patches x 100 points, k = 32, k_scales = [8, 16, 32, 48], T = 7, emb_dims = 768, num_heads = 8, dropout 0.1; AdamW, grad_clip 0.1.
 
-    python profiles/fd_train_step.py [--steps 10] [--warmup 3] [--out FILE]
+    python profiles/fd_train_step.py [--steps 10] [--warmup 3] [--precision f32|bf16] [--edgeconv feature|factored] [--out FILE]
+
+The default (f32, feature) is fd_trainer.Trainer's step; anything else runs fd_trainer.AmpTrainer.  --out appends.
 
 Prints (and writes to --out) one JSON line.  The launch count is the number of device kernels torch's profiler sees in one step
 (HIP ops of the library and torch's own element-wise / optimiser kernels alike)."""
@@ -20,6 +22,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
+    ap.add_argument("--edgeconv", choices=("feature", "factored"), default="feature")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import sapcu_amd
@@ -30,7 +34,10 @@ def main():
     model = sapcu_amd.TrainableSNNDistanceEstimation(**kw).to(dev)
     model.dropout_generator = torch.Generator(device=dev).manual_seed(1)
     opt = torch.optim.AdamW(model.parameters(), lr=1e-4)
-    trainer = fd_trainer.Trainer(model, opt, device=dev, grad_clip=0.1)
+    if a.precision == "f32" and a.edgeconv == "feature":
+        trainer = fd_trainer.Trainer(model, opt, device=dev, grad_clip=0.1)
+    else:
+        trainer = fd_trainer.AmpTrainer(model, opt, device=dev, grad_clip=0.1, use_amp=a.precision == "bf16", edgeconv=a.edgeconv)
     batches = list(fd_trainer.SyntheticFdPatches(batches=a.warmup + a.steps + 1, batch_size=4, patches=16, points=100, seed=0))
     losses = []
     for b in batches[:a.warmup]:
@@ -51,14 +58,14 @@ def main():
         launches = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA"))
     except Exception as e:                                   # the profiler is optional: the timing stands without it
         print("profiler unavailable: %r" % (e,), file=sys.stderr)
-    res = {"what": "fd training step, f32", "shape": "4 clouds x 16 patches x 100 points", "model": kw, "steps": a.steps, "warmup": a.warmup,
+    res = {"what": "fd training step, %s, %s EdgeConv" % (a.precision, a.edgeconv), "shape": "4 clouds x 16 patches x 100 points", "model": kw, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": round(dt * 1e3, 2), "clouds_per_s": round(4 / dt, 2), "device_kernels_per_step": launches,
            "peak_memory_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "first_loss": losses[0], "last_loss": losses[-1],
            "device": torch.cuda.get_device_name(0)}
     line = json.dumps(res)
     print(line)
     if a.out:
-        with open(a.out, "w") as f:
+        with open(a.out, "a") as f:
             f.write(line + "\n")
 
 
