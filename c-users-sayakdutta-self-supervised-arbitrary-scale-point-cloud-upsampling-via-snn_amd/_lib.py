@@ -123,6 +123,12 @@ _FD_EDGECONV_SIGNATURES = {
 }
 FD_EDGECONV_EXPORTS = tuple(_FD_EDGECONV_SIGNATURES)
 
+# include/sapcu_train_step.h: the device-side skip of a graphed training step (a fifth table); flag, dst, src and nbytes are DEVICE arrays
+_TRAIN_STEP_SIGNATURES = {
+    "sapcu_multi_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+}
+TRAIN_STEP_EXPORTS = tuple(_TRAIN_STEP_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -145,7 +151,7 @@ def load(path=None):
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
-            list(_FD_EDGECONV_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

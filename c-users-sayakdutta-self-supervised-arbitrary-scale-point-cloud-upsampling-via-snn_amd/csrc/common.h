@@ -562,6 +562,10 @@ int launch_displace(const double* q, const float* nrm, const float* d, int64_t b
 
 // farthest-point sampling (fps.hip)
 size_t fps_workspace_bytes(int npoint);
+// *p = 0 on `st`, for the bad_count slots of the training ops.  hipMemsetAsync, except while `st` is being captured: as a memset
+// NODE of the fd training step's graph the 4-byte zeroing was seen to leave a byte-uniform non-zero value in the slot on replay
+// (0x01010101), so a captured call zeroes with a one-lane kernel node instead (train_step_ops.hip).
+int zero_count(int* p, hipStream_t st);
 int launch_fps(const float* xyz, int64_t n, int npoint, int start, int64_t* out, void* ws, hipStream_t st);
 int fps_failed(const void* ws, int npoint, int* flag);
 

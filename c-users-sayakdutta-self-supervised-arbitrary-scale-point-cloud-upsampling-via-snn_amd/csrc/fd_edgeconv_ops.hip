@@ -326,7 +326,7 @@ int sapcu_fd_edgeconv_stats(const float* ab, const int32_t* idx, int64_t patches
     const EcStatsWs L = ec_stats_ws_layout(workspace, pts, channels);
     const int64_t nb = ec_blocks(pts, EC_STAT_PTS);
     const unsigned tiles = (unsigned)((channels + 63) / 64);
-    if (bad_count) SAPCU_CHECK_HIP(hipMemsetAsync(bad_count, 0, sizeof(int), st));
+    if (bad_count) { const int zrc = zero_count(bad_count, st); if (zrc != SAPCU_OK) return zrc; }
     hipLaunchKernelGGL(ec_stats_partial_kernel, dim3((unsigned)nb, tiles), dim3(256), 0, st, ab, idx, pts, m, kk, channels, L.partial,
                        bad_count);
     SAPCU_CHECK_LAUNCH();
@@ -374,7 +374,7 @@ int sapcu_fd_edgeconv_backward(const float* ab, const int32_t* idx, const float*
     const EcBwdWs L = ec_bwd_ws_layout(workspace, pts, channels);
     const int64_t nb = ec_blocks(pts, EC_GZ_PTS);
     const unsigned tiles = (unsigned)((channels + 63) / 64);
-    SAPCU_CHECK_HIP(hipMemsetAsync(bad_count, 0, sizeof(int), st));
+    { const int zrc = zero_count(bad_count, st); if (zrc != SAPCU_OK) return zrc; }
     hipLaunchKernelGGL(ec_gz_partial_kernel, dim3((unsigned)nb, tiles), dim3(256), 0, st, ab, idx, grad_out, argmax, pts, m, kk, channels,
                        mean, invstd, gamma, beta, L.gzv, L.partial);
     SAPCU_CHECK_LAUNCH();

@@ -391,7 +391,7 @@ int sapcu_fd_edge_feature_forward(const float* x, int ldx, const int32_t* idx, i
     SAPCU_CHECK_ARG(x && idx && out, "fd_edge_feature_forward: null pointer");
     SAPCU_CHECK_ARG(edge_feature_args_ok(patches, m, kk, channels, out_channels) && ldx >= channels,
                     "fd_edge_feature_forward: bad shape (need out_channels >= 2 channels, ldx >= channels)");
-    if (bad_count) SAPCU_CHECK_HIP(hipMemsetAsync(bad_count, 0, sizeof(int), (hipStream_t)stream));
+    if (bad_count) { const int zrc = zero_count(bad_count, (hipStream_t)stream); if (zrc != SAPCU_OK) return zrc; }
     const int64_t edges = patches * m * kk;
     if (edges == 0) return SAPCU_OK;
     hipLaunchKernelGGL(edge_feature_fwd_kernel, dim3((unsigned)((edges * out_channels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
@@ -407,7 +407,7 @@ int sapcu_fd_edge_feature_backward(const float* grad_out, const int32_t* idx, in
                     "fd_edge_feature_backward: bad shape (need out_channels >= 2 channels, ld_grad >= channels)");
     const size_t lds = ((size_t)2 * m * kk + m + 1) * sizeof(int);
     SAPCU_CHECK_ARG(lds <= 64 * 1024, "fd_edge_feature_backward: patch too large (%d points x %d neighbours)", m, kk);
-    SAPCU_CHECK_HIP(hipMemsetAsync(bad_count, 0, sizeof(int), (hipStream_t)stream));
+    { const int zrc = zero_count(bad_count, (hipStream_t)stream); if (zrc != SAPCU_OK) return zrc; }
     if (patches == 0) return SAPCU_OK;
     hipLaunchKernelGGL(edge_feature_bwd_kernel, dim3((unsigned)patches), dim3(256), lds, (hipStream_t)stream, grad_out, idx, m, kk,
                        channels, out_channels, grad_x, ld_grad, bad_count);

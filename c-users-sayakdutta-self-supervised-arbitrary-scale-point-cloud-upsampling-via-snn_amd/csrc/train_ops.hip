@@ -843,7 +843,7 @@ int sapcu_scatter_add_rows_grouped(const float* grad_out, const int64_t* index, 
                     "scatter_add_rows_grouped: %lld rows / %d and %lld destination rows / %d are not the same number of whole groups",
                     (long long)rows, group_rows, (long long)src_rows, group_src_rows);
     // the kernel only adds to the counter: zero it here, on the call's stream, so that the result does not depend on what it held
-    if (bad_count) SAPCU_CHECK_HIP(hipMemsetAsync(bad_count, 0, sizeof(int), (hipStream_t)stream));
+    if (bad_count) { const int zrc = zero_count(bad_count, (hipStream_t)stream); if (zrc != SAPCU_OK) return zrc; }
     return launch_scatter_sum_grouped(grad_out, nullptr, index, rows / group_rows, group_src_rows, group_rows, d, grad_src, ld_grad,
                                       bad_count, (hipStream_t)stream);
 }

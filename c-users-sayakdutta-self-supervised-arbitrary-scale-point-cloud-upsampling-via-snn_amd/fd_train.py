@@ -18,7 +18,10 @@ bf16: every GEMM / weight gradient here goes through ``train._gemm`` / ``_wgrad`
 ``edgeconv_form("factored")`` runs blocks 1-3 through ``edgeconv_factored`` (include/sapcu_fd_edgeconv.h, csrc/fd_edgeconv_ops.hip),
 which never builds the [P M kk, 2C] edge tensors.  ``fd_trainer.AmpTrainer`` drives both, a GradScaler and gradient accumulation.
 
-Not built, and refused where a caller could ask for it: HIP-graph capture of the step, ``use_snn_decoder=True``, DataParallel.
+``fd_trainer.GraphedTrainStep`` replays the whole step as one HIP graph: nothing here synchronises or reads the device (the
+bad-index counter is a device tensor, ``bad_index_counter``), and a replay leaves exactly the state the eager step leaves.
+
+Not built, and refused where a caller could ask for it: ``use_snn_decoder=True``, DataParallel.
 The decoder works on [P, <= 256] tensors: its Linear / BatchNorm layers are the HIP ops of
 train.py, GELU, LayerNorm, the softmax over heads, Softplus, the loss and the dropout masks are torch ops, as in fn's training.
 """
@@ -43,6 +46,18 @@ def _check_patch_shape(M, kk):
     if (2 * M * kk + M + 1) * 4 > EDGE_LDS_LIMIT:
         raise ValueError("EdgeConv training op: %d points x %d neighbours per patch need %d bytes of LDS in the backward, the limit is %d"
                          % (M, kk, (2 * M * kk + M + 1) * 4, EDGE_LDS_LIMIT))
+
+
+def bad_index_counter(device):
+    """The int32 [1] counter of `device`, created (zero) on first use.  A HIP-graph capture of the step needs it to exist before
+    the capture begins — a tensor created inside one would be zeroed again by every replay."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    acc = _BAD.get(device)
+    if acc is None:
+        acc = _BAD[device] = torch.zeros((1,), dtype=torch.int32, device=device)
+    return acc
 
 
 def take_bad_index_count():
@@ -135,10 +150,7 @@ def _edge_feature_backward(g, idx, c):
     with torch.cuda.device(g.device):
         _lib.check(lib.sapcu_fd_edge_feature_backward(_lib.ptr(g), _lib.ptr(idx), P, M, kk, c, g.shape[1], _lib.ptr(gx), c, _lib.ptr(bad),
                                                       _lib.current_stream()))
-    acc = _BAD.get(g.device)
-    if acc is None:
-        acc = _BAD[g.device] = torch.zeros((1,), dtype=torch.int32, device=g.device)
-    acc.add_(bad)
+    bad_index_counter(g.device).add_(bad)
     return gx
 
 
@@ -288,10 +300,7 @@ class edgeconv_form(object):
 
 
 def _count_bad(bad):
-    acc = _BAD.get(bad.device)
-    if acc is None:
-        acc = _BAD[bad.device] = torch.zeros((1,), dtype=torch.int32, device=bad.device)
-    acc.add_(bad)
+    bad_index_counter(bad.device).add_(bad)
 
 
 def _edgeconv_factored_forward(lib, x, wst, idx, ga, be, eps):

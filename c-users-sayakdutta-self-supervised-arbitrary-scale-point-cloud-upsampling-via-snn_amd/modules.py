@@ -438,7 +438,9 @@ class TrainableSNNDistanceEstimation(EnhancedSNNDistanceEstimation):
     bf16 GEMM operands, a GradScaler, gradient accumulation and the factored EdgeConv of blocks 1-3 are ``fd_trainer.AmpTrainer``'s
     (``train.gemm_precision`` / ``fd_train.edgeconv_form`` around forward and backward).
 
-    Not built (refused or absent, never emulated): HIP-graph capture of the step, ``use_snn_decoder=True``, DataParallel."""
+    ``fd_trainer.GraphedTrainStep`` replays a whole step of either trainer as one HIP graph, equal to the eager step bit for bit.
+
+    Not built (refused or absent, never emulated): ``use_snn_decoder=True``, DataParallel."""
 
     def __init__(self, k=20, emb_dims=512, time_steps_enc=5, time_steps_dec=8, num_heads=4, dropout=0.1, use_snn_decoder=False,
                  k_scales=[10, 20, 40]):
