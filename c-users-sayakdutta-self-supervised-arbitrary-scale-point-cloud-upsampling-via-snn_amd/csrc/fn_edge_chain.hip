@@ -28,6 +28,14 @@
 // d = 128: 256-thread workgroups, 51 KiB of LDS, three per CU.  d = 256: 512 threads, 131 KiB, one per CU.  d = 512: 512 threads (wave
 // tile 64 x 64), 131 KiB.  What bounds them (each pipe at its practical rate, the kernel time their sum) and the overlap designs that
 // were measured without gain: DESIGN.md section 4.1c.
+// Trimmed epilogues (template parameter TRIM, a.trim, SAPCU_CHAIN_TRIM=0 turns them off for a handle; same bits either way).  The
+// phases between the GEMMs run with the matrix pipe idle, so VALU work that is not the neuron loop comes off the kernel time:
+//   - a point that lives in spare slots (d = 256: three of seven, d = 512: one of five) is summed by the lane groups that HOLD its
+//     rows, the softmax's two sequential sums handed from lane group to lane group in neighbour order (five / seven lane exchanges
+//     per column sub-block, issued in front of halves of the own points' softmax), instead of by every lane group over copies
+//     fetched with two swaps per value;
+//   - d = 256: fc_delta (phase 0) is one v_mfma_f32_16x16x4_f32 per 16 x 16 block, which computes exactly the VALU form's chain.
+// -DCHAIN_STAMPS (profiles/chain_stamps.py) records where a group's time goes.
 #include "common.h"
 #include "gemm_epi.h"
 #include "ops.h"
@@ -44,6 +52,12 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 // 4.64 -> 4.42 -> 3.93 -> 3.8 (three workgroups per CU: the k32 step's operand fragments half the row sub-blocks at a time, 160 registers).
 #ifndef SAPCU_CHAIN_LB128
 #define SAPCU_CHAIN_LB128 3
+#endif
+// Block shapes whose trimmed form computes fc_delta on the exact-f32 MFMA (fn_edge_chain_body, phase 0).  d = 256 only: the stamps
+// (profiles/r11_chain_stamps.txt) show phase 0 shorter by 2.9 % there, unchanged at d = 128 and within the run-to-run difference of
+// untouched phases at d = 512.  -DSAPCU_CHAIN_FCD_MFMA(D)=true builds it for all three.
+#ifndef SAPCU_CHAIN_FCD_MFMA
+#define SAPCU_CHAIN_FCD_MFMA(D) ((D) == 256)
 #endif
 // Round 3, late: the GEMMs issue v_mfma_f32_16x16x32_f16.  Same flops per cycle as the 32x32x16 shape, but the chip holds a higher
 // clock on it (profiles/micro/mfma_shape.hip: 1.82 against 1.60 GHz, two waves per SIMD, random operands), and one 16x16x32 equals
@@ -131,6 +145,47 @@ __device__ __forceinline__ float group_bcast(float x, int s) {
     const auto q = __builtin_amdgcn_permlane32_swap(z, z, false, false);     // q[0] = [lo,lo], q[1] = [hi,hi]
     return __uint_as_float((s & 2) ? q[1] : q[0]);
 }
+
+// x of the lane whose number is byte_addr / 4 (ds_bpermute: the LDS crossbar, no LDS memory)
+__device__ __forceinline__ float lane_fetch(int byte_addr, float x) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(x)));
+}
+
+// diagnostic build (-DCHAIN_STAMPS, profiles/chain_stamps.py): s_memtime at the phase boundaries as thread 0 passes them, 16 slots
+// per group in a.stamps (sapcu_fn_edge_chain_f32: the workspace's bytes behind what the entry needs).  Slots: 0 start, 1 edge records
+// read, 2 phase 0 done, 3 GEMM 1 starts, 4 GEMM 1 done, 5 epilogue 1 starts, 6 done, 7 GEMM 2 starts, 8 done, 9 epilogue 2 starts,
+// 10 done, 11 GEMM 3 starts, 12 done, 13 / 14 ticks of the last epilogue spent on the lane groups' own points / on the points in
+// spare slots, 15 end.
+#ifdef CHAIN_STAMPS
+#define CHAIN_STAMP(IDX)                                                                                 \
+    do {                                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        if (a.stamps && tid == 0) a.stamps[grp * 16 + (IDX)] = __builtin_amdgcn_s_memtime();             \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+    } while (0)
+#define CHAIN_T0() unsigned long long ch_t_own = 0, ch_t_spare = 0, ch_tp = __builtin_amdgcn_s_memtime()
+#define CHAIN_TACC(V)                                                          \
+    do {                                                                       \
+        __builtin_amdgcn_sched_barrier(0);                                     \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
+        ch_##V += now_ - ch_tp;                                                \
+        ch_tp = now_;                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                     \
+    } while (0)
+#define CHAIN_STAMP_END()                                                      \
+    do {                                                                       \
+        if (a.stamps && tid == 0) {                                            \
+            a.stamps[grp * 16 + 13] = ch_t_own;                                \
+            a.stamps[grp * 16 + 14] = ch_t_spare;                              \
+            a.stamps[grp * 16 + 15] = __builtin_amdgcn_s_memtime();            \
+        }                                                                      \
+    } while (0)
+#else
+#define CHAIN_STAMP(IDX) do { } while (0)
+#define CHAIN_T0() do { } while (0)
+#define CHAIN_TACC(V) do { } while (0)
+#define CHAIN_STAMP_END() do { } while (0)
+#endif
 
 template <int CS>
 struct ChainLane {       // per-lane constants of the epilogues
@@ -306,8 +361,10 @@ __device__ __forceinline__ float group_select(float v0, float v1, float v2, floa
 }
 
 // per-point softmax over the kk neighbours and aggregation with t = v_j + pe, fn_softmax_agg_kernel's operation order
+// (in two halves, so that the trimmed last epilogue can put other work between them: the maximum, the exponentials — left in xs — and
+// their sum; then the weights and the aggregate)
 template <int KK>
-__device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float (&ts)[KK]) {
+__device__ __forceinline__ float chain_softmax_den(float (&xs)[KK]) {
     float mx = -__builtin_huge_valf();
 #pragma unroll
     for (int jj = 0; jj < KK; ++jj) mx = fmaxf(mx, xs[jj]);
@@ -323,6 +380,11 @@ __device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float 
         den = __fadd_rn(den, xs[jj]);
         den = __fadd_rn(den, xs[jj + 1]);
     }
+    return den;
+}
+
+template <int KK>
+__device__ __forceinline__ float chain_softmax_out(const float (&xs)[KK], const float (&ts)[KK], float den) {
     const float inv_den = __fdiv_rn(1.0f, den);
     const f32x2 inv2 = f32x2{inv_den, inv_den};
     float out = 0.f;
@@ -333,6 +395,12 @@ __device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float 
         out = __fmaf_rn(w2.y, ts[jj + 1], out);
     }
     return out;
+}
+
+template <int KK>
+__device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float (&ts)[KK]) {
+    const float den = chain_softmax_den<KK>(xs);
+    return chain_softmax_out<KK>(xs, ts, den);
 }
 
 // threads = 64 x (d / 32 / CB).  d = 128: three 256-thread workgroups per CU (51 KiB of LDS each, <= 170 registers per wave).
@@ -349,14 +417,18 @@ __device__ __forceinline__ float chain_softmax_agg(float (&xs)[KK], const float 
 // straddler's q_i in the GEMM-1 epilogue) but its 12 rows end in three workgroups: lane group 3 stores their scaled logits and
 // t = v_j + pe to two scratch tensors [P / 16][12][d], and fn_chain_straddler_kernel, launched behind this kernel on the same stream,
 // runs the same chain_softmax_agg over them.  Same products, same order, same softmax routine: the bits of the plain grouping.
-template <int D, int KK, bool O32, bool FILL>
+template <int D, int KK, bool O32, bool FILL, bool TRIM>
 __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
     static_assert(!FILL || (D == 512 && KK == 12), "filled groups: d = 512, kk = 12");
+    static_assert(ChainSlots<D, KK>::NUA == 0 || (ChainSlots<D, KK>::NUA == 1 && ChainSlots<D, KK>::SP == 4 && KK == 12) ||
+                      (ChainSlots<D, KK>::NUA == 3 && ChainSlots<D, KK>::SP == 14 && KK == 18),
+                  "the trimmed spare-slot sums are written for the slot layouts of d = 256 / kk = 18 and d = 512 / kk = 12");
     using S = ChainShape<D>;
     using M = ChainSlots<D, KK>;
     constexpr int CH_ROWS = S::ROWS, RS = S::RS, CS = S::CS, CH_PLANE = S::PLANE, CH_KSTEP = S::KSTEP;
     constexpr int PPG = M::PPG, NUA = M::NUA, SP = M::SP;
     constexpr int NUP = RS / 2;                            // epilogue units per column sub-block: the quads of row sub-blocks 2 up, 2 up + 1
+    constexpr bool TRIM_FCD = TRIM && SAPCU_CHAIN_FCD_MFMA(D);      // fc_delta on the matrix pipe (phase 0)
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     unsigned char* X = smem;
     // position differences of the group's slots, one array per coordinate: the four rows of a register quad are 16 contiguous bytes,
@@ -410,6 +482,7 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
 
     f32x4 acc[RS][CS], pe[RS][CS];
     ChainW<CS> W;
+    CHAIN_STAMP(0);
     // ---- phase 0: edge records of the group's slots; pe1 = LIF(fc_delta(x_i - x_j)) -> panel              fn:310,355-358
     if (tid < CH_ROWS) {
         const int rs = tid >> 4, sg = (tid >> 2) & 3, e = tid & 3, t = 4 * rs + e;
@@ -432,29 +505,64 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
         pdx[tid] = dv.x;
         pdy[tid] = dv.y;
         pdz[tid] = dv.z;
+        if (TRIM_FCD) pdz[CH_ROWS + tid] = 1.0f;              // fourth operand array (the bias term's factor): the 4 bytes per row the three leave
     }
+    CHAIN_STAMP(1);
     lds_barrier();                                         // edge records are in
+    // TRIM_FCD: fc_delta on the matrix pipe.  The value is the k-ascending chain (((dx wx) + dy wy) + dz wz) + 1 b of fn_pe1_kernel, and a
+    // k-ascending chain of IEEE f32 FMAs is what v_mfma_f32_16x16x4_f32 computes (profiles/micro/mfma_f32_exact.hip; fd's block-0
+    // EdgeConv).  A[row][k] = dx / dy / dz / 1 of slot 16 rs + row: ONE dword per lane and row sub-block, shared by all column
+    // sub-blocks; B[k][col] = wd[3 col + k] or bd[col]: one register per column sub-block; the block lands in the accumulator layout
+    // the neuron loop reads (lane -> column l & 15, rows 4 (l >> 4) + e).  The accumulator starts from -0: fma(dx, wx, -0) =
+    // round(dx wx) with the sign the multiply gives it (+0 would turn a product of -0 into +0), and fma(1, b, s) = s + b.  The two
+    // MFMAs of unit u + 1 are issued in front of the neuron arithmetic of unit u and run in its shadow.
+    float pa[RS], wb[CS];
+    auto fc_delta_unit = [&](int j, int up) {
+#pragma unroll
+        for (int hq = 0; hq < 2; ++hq)
+            acc[2 * up + hq][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[2 * up + hq], wb[j], f32x4{-0.f, -0.f, -0.f, -0.f}, 0, 0, 0);
+    };
+    if (TRIM_FCD) {
+#pragma unroll
+        for (int i = 0; i < RS; ++i) pa[i] = pdx[L.g * CH_ROWS + 16 * i + L.c16];
+#pragma unroll
+        for (int j = 0; j < CS; ++j) wb[j] = L.g < 3 ? a.wd[L.col[j] * 3 + L.g] : a.bd[L.col[j]];
+        fc_delta_unit(0, 0);
+    }
 #pragma unroll
     for (int j = 0; j < CS; ++j) {
         // accumulator layout, like the epilogues: this lane's column for its rows (the neuron parameters are per-lane constants;
-        // the position differences are LDS broadcasts)
-        const float wx = a.wd[L.col[j] * 3], wy = a.wd[L.col[j] * 3 + 1], wz = a.wd[L.col[j] * 3 + 2], bd = a.bd[L.col[j]];
+        // untrimmed form: the position differences are LDS broadcasts)
+        float wx = 0.f, wy = 0.f, wz = 0.f, bd = 0.f;
+        if (!TRIM_FCD) {
+            wx =a.wd[L.col[j] * 3];
+            wy = a.wd[L.col[j] * 3 + 1];
+            wz = a.wd[L.col[j] * 3 + 2];
+            bd = a.bd[L.col[j]];
+        }
         const NeuronP nd = chain_lif(a.lifd, D, L.col[j]);
 #pragma unroll
         for (int up = 0; up < NUP; ++up) {
             float v[8];
+            if (TRIM_FCD) {
+                if (up + 1 < NUP) fc_delta_unit(j, up + 1);
+                else if (j + 1 < CS) fc_delta_unit(j + 1, 0);
 #pragma unroll
-            for (int hq = 0; hq < 2; ++hq) {               // the two quads of the unit; element-wise mul, fma, fma, add as fn_pe1_kernel
-                const int r0 = 16 * (2 * up + hq) + rowg;
-                const float4 qx = *reinterpret_cast<const float4*>(pdx + r0), qy = *reinterpret_cast<const float4*>(pdy + r0),
-                             qz = *reinterpret_cast<const float4*>(pdz + r0);
-                const f32x2 wx2 = f32x2{wx, wx}, wy2 = f32x2{wy, wy}, wz2 = f32x2{wz, wz}, bd2 = f32x2{bd, bd};
-                const f32x2 ta = pk_fma(wz2, f32x2{qz.x, qz.y}, pk_fma(wy2, f32x2{qy.x, qy.y}, wx2 * f32x2{qx.x, qx.y})) + bd2;
-                const f32x2 tb = pk_fma(wz2, f32x2{qz.z, qz.w}, pk_fma(wy2, f32x2{qy.z, qy.w}, wx2 * f32x2{qx.z, qx.w})) + bd2;
-                v[4 * hq] = ta.x;
-                v[4 * hq + 1] = ta.y;
-                v[4 * hq + 2] = tb.x;
-                v[4 * hq + 3] = tb.y;
+                for (int z = 0; z < 8; ++z) v[z] = acc[2 * up + (z >> 2)][j][z & 3];
+            } else {
+#pragma unroll
+                for (int hq = 0; hq < 2; ++hq) {           // the two quads of the unit; element-wise mul, fma, fma, add as fn_pe1_kernel
+                    const int r0 = 16 * (2 * up + hq) + rowg;
+                    const float4 qx = *reinterpret_cast<const float4*>(pdx + r0), qy = *reinterpret_cast<const float4*>(pdy + r0),
+                                 qz = *reinterpret_cast<const float4*>(pdz + r0);
+                    const f32x2 wx2 = f32x2{wx, wx}, wy2 = f32x2{wy, wy}, wz2 = f32x2{wz, wz}, bd2 = f32x2{bd, bd};
+                    const f32x2 ta = pk_fma(wz2, f32x2{qz.x, qz.y}, pk_fma(wy2, f32x2{qy.x, qy.y}, wx2 * f32x2{qx.x, qx.y})) + bd2;
+                    const f32x2 tb = pk_fma(wz2, f32x2{qz.z, qz.w}, pk_fma(wy2, f32x2{qy.z, qy.w}, wx2 * f32x2{qx.z, qx.w})) + bd2;
+                    v[4 * hq] = ta.x;
+                    v[4 * hq + 1] = ta.y;
+                    v[4 * hq + 2] = tb.x;
+                    v[4 * hq + 3] = tb.y;
+                }
             }
             lif_selfloop_n<8>(v, nd, a.T);
 #pragma unroll
@@ -462,6 +570,7 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    CHAIN_STAMP(2);
     const half8* const wp1 = reinterpret_cast<const half8*>(a.w1p);
     const half8* const wp2 = reinterpret_cast<const half8*>(a.w2p);
     const half8* const wp3 = reinterpret_cast<const half8*>(a.w3p);
@@ -494,11 +603,14 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
     gather_kv(0, 0, kq[0], vq[0]);                         // in flight during GEMM 1
     chain_w_prefetch<D>(wp1, cs0, lane, W);
     lds_barrier();                                         // pe1 panel complete
+    CHAIN_STAMP(3);
 
     // ---- GEMM 1: fc_delta2; epilogue pe = LIF(.), attn_in = q_i - k_j + pe -> panel, t = v_j + pe stays      fn:360-368
     {
         chain_gemm<D>(X, wp1, cs0, lane, W, acc);
+        CHAIN_STAMP(4);
         lds_barrier();                                     // every wave has read the pe1 panel: it may be overwritten
+        CHAIN_STAMP(5);
         // software pipeline over the units: the gathers of unit u + 1 are issued before the neuron arithmetic of unit u
         // and consumed after the one of unit u + 1 (the in-order vector-memory counter then waits for loads that are one
         // arithmetic block old)
@@ -546,13 +658,17 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        CHAIN_STAMP(6);
         chain_w_prefetch<D>(wp2, cs0, lane, W);
     }
     lds_barrier();                                         // attn_in panel complete
+    CHAIN_STAMP(7);
     // ---- GEMM 2: fc_gamma; epilogue g = LIF(.) -> panel                                                   fn:373-376
     {
         chain_gemm<D>(X, wp2, cs0, lane, W, acc);
+        CHAIN_STAMP(8);
         lds_barrier();
+        CHAIN_STAMP(9);
 #pragma unroll
         for (int j = 0; j < CS; ++j) {
             const float b2 = a.b2[L.col[j]];
@@ -568,16 +684,19 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
+        CHAIN_STAMP(10);
         chain_w_prefetch<D>(wp3, cs0, lane, W);
     }
     lds_barrier();                                         // g panel complete
+    CHAIN_STAMP(11);
     // ---- GEMM 3: fc_gamma2; per-point softmax over the kk neighbours, aggregation with v_j + pe           fn:378-389
     {
         chain_gemm<D>(X, wp3, cs0, lane, W, acc);
-#pragma unroll
-        for (int j = 0; j < CS; ++j) {
+        CHAIN_STAMP(12);
+        CHAIN_T0();
+        // rows of column sub-block j: x = (a + b) / sqrt(hd) in place of the accumulators (pe already holds t = v_j + pe)
+        auto scale_rows = [&](int j) {
             const float b3 = a.b3[L.col[j]];
-            // own rows: x = (a + b) / sqrt(hd) in place of the accumulators (pe already holds t = v_j + pe)
 #pragma unroll
             for (int i = 0; i < RS; ++i) {                 // (packed: fma, then mul, per element as fn_softmax_agg_kernel)
                 const f32x2 k16 = f32x2{0.0625f, 0.0625f}, b32 = f32x2{b3, b3}, is2 = f32x2{a.inv_sqrt_hd, a.inv_sqrt_hd};
@@ -596,57 +715,256 @@ __device__ __forceinline__ void fn_edge_chain_body(const ChainArgs& a) {
                     }
                 }
             }
-            // lane group g's own point: its kk rows are this lane's registers, in neighbour order
-            {
-                float xs[KK], ts[KK];
+        };
+        // lane group g's own point: its kk rows are this lane's registers, in neighbour order.  First half: maximum, exponentials (they
+        // replace the logits) and den; second half: weights, aggregate, store.
+        float own_den[CS];
+        auto own_first = [&](int j) {
+            float xs[KK];
 #pragma unroll
-                for (int jj = 0; jj < KK; ++jj) {
-                    xs[jj] = acc[jj >> 2][j][jj & 3];
-                    ts[jj] = pe[jj >> 2][j][jj & 3];
-                }
-                const float out = chain_softmax_agg<KK>(xs, ts);
-                if (L.g < npts) {
-                    const int64_t pt = pt0 + L.g;
-                    if (a.res_split) chain_store_split_nt(a.res, pt, D, L.col[j], out);
-                    else __builtin_nontemporal_store(out, &a.res[pt * D + L.col[j]]);
-                }
+            for (int jj = 0; jj < KK; ++jj) xs[jj] = acc[jj >> 2][j][jj & 3];
+            own_den[j] = chain_softmax_den<KK>(xs);
+#pragma unroll
+            for (int jj = 0; jj < KK; ++jj) acc[jj >> 2][j][jj & 3] = xs[jj];
+        };
+        auto own_second = [&](int j) {
+            float xs[KK], ts[KK];
+#pragma unroll
+            for (int jj = 0; jj < KK; ++jj) {
+                xs[jj] = acc[jj >> 2][j][jj & 3];
+                ts[jj] = pe[jj >> 2][j][jj & 3];
             }
-            // the points in the spare slots: point 4 + n is summed by lane group n, which fetches the point's values from the lane
-            // groups that hold them (two swaps per value and source; a value no lane group asks for costs nothing)
-            if (NUA > 0) {
-                float xs[KK], ts[KK];
+            const float out = chain_softmax_out<KK>(xs, ts, own_den[j]);
+            if (L.g < npts) {
+                const int64_t pt = pt0 + L.g;
+                if (a.res_split) chain_store_split_nt(a.res, pt, D, L.col[j], out);
+                else __builtin_nontemporal_store(out, &a.res[pt * D + L.col[j]]);
+            }
+        };
+        if constexpr (!(NUA > 0 && TRIM)) {
 #pragma unroll
-                for (int jj = 0; jj < KK; ++jj) {
-                    float cx[4] = {0.f, 0.f, 0.f, 0.f}, ct[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < CS; ++j) {
+                scale_rows(j);
+                own_first(j);
+                own_second(j);
+                CHAIN_TACC(t_own);
+                // the points in the spare slots, untrimmed form: point 4 + n is summed by lane group n, which fetches the point's values
+                // from the lane groups that hold them (two swaps per value and source; a value no lane group asks for costs nothing)
+                if (NUA > 0) {
+                    float xs[KK], ts[KK];
 #pragma unroll
-                    for (int n = 0; n < NUA; ++n) {
-                        const int rs = M::ua_rs(n, jj), e = M::ua_e(n, jj), sg = M::ua_g(n, jj);
-                        cx[n] = group_bcast(acc[rs][j][e], sg);
-                        ct[n] = group_bcast(pe[rs][j][e], sg);
+                    for (int jj = 0; jj < KK; ++jj) {
+                        float cx[4] = {0.f, 0.f, 0.f, 0.f}, ct[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int n = 0; n < NUA; ++n) {
+                            const int rs = M::ua_rs(n, jj), e = M::ua_e(n, jj), sg = M::ua_g(n, jj);
+                            cx[n] = group_bcast(acc[rs][j][e], sg);
+                            ct[n] = group_bcast(pe[rs][j][e], sg);
+                        }
+                        xs[jj] = NUA == 1 ? cx[0] : group_select(cx[0], cx[1], cx[2], cx[3], g0, g1);
+                        ts[jj] = NUA == 1 ? ct[0] : group_select(ct[0], ct[1], ct[2], ct[3], g0, g1);
                     }
-                    xs[jj] = NUA == 1 ? cx[0] : group_select(cx[0], cx[1], cx[2], cx[3], g0, g1);
-                    ts[jj] = NUA == 1 ? ct[0] : group_select(ct[0], ct[1], ct[2], ct[3], g0, g1);
+                    const float out = chain_softmax_agg<KK>(xs, ts);
+                    if (L.g < NUA && 4 + L.g < npts) {
+                        const int64_t pt = pt0 + 4 + L.g;
+                        if (a.res_split) chain_store_split_nt(a.res, pt, D, L.col[j], out);
+                        else __builtin_nontemporal_store(out, &a.res[pt * D + L.col[j]]);
+                    }
                 }
-                const float out = chain_softmax_agg<KK>(xs, ts);
-                if (L.g < NUA && 4 + L.g < npts) {
-                    const int64_t pt = pt0 + 4 + L.g;
-                    if (a.res_split) chain_store_split_nt(a.res, pt, D, L.col[j], out);
-                    else __builtin_nontemporal_store(out, &a.res[pt * D + L.col[j]]);
+                CHAIN_TACC(t_spare);
+            }
+        } else {
+            // The points in the spare slots, trimmed form: every lane group reduces the slots it HOLDS, and the running sums travel from
+            // lane group to lane group in neighbour order.  A spare point's neighbours sit in neighbour order in consecutive lane groups
+            // (ChainSlots::ua_g), so chain_softmax_agg's two sequential sums, den += e_jj and out = fma(w_jj, t_jj, out), are continued
+            // where the previous lane group stopped: same additions in the same order, the same bits.  The maximum is exact in any
+            // order; every exponential is taken once, by the lane that holds the logit; the one division is done where the den chain
+            // ends and its quotient sent back.  The lane group where a point's chain ends stores its row.
+            // The work goes in STAGES, each ending with one lane exchange per column sub-block (ds_bpermute: the LDS crossbar, no
+            // memory), and a stage is followed by half of an own point's softmax, so that the exchange is in flight under arithmetic
+            // that does not wait for it.
+            // Spare slot s of a lane group = registers (rs, e) = ((KK + s) >> 2, (KK + s) & 3); exponentials and weights replace the logits.
+#define CHAIN_SX(J, S) acc[(KK + (S)) >> 2][J][(KK + (S)) & 3]
+#define CHAIN_ST(J, S) pe[(KK + (S)) >> 2][J][(KK + (S)) & 3]
+#pragma unroll
+            for (int j = 0; j < CS; ++j) scale_rows(j);
+            const int a_prev = ((lane + 48) & 63) * 4, a_next = ((lane + 16) & 63) * 4;      // same column, lane group g - 1 / g + 1
+            const float NEG = -__builtin_huge_valf();
+            const f32x2 l2e = f32x2{1.4426950408889634074f, 1.4426950408889634074f};
+            constexpr int NST = NUA == 3 ? 5 : 7, NH = 2 * CS;
+            float o_end[CS], u0[CS], u1[CS], u2[CS], u3[CS];
+            // d = 256: lane group g holds 14 spare slots; its slots s < 4 g FINISH point 3 + g (neighbours 18 - 4 g .. 17, started by
+            // lane group g - 1), the others START point 4 + g (neighbours 0 .. 13 - 4 g, finished by lane group g + 1); lane group 3's
+            // slots 12 and 13 are idle.  The slot indices are compile-time, so the slots go in QUADS q = s >> 2 and a lane keeps a quad's
+            // partial chain by one select: quad q finishes (fin) where q < g, else starts (q = 3: idle in lane group 3).  Lanes compute
+            // both chains over all quads; what a select drops is never read.
+            const bool fin[3] = {L.g > 0, L.g > 1, L.g > 2};
+            auto finishes = [&](int q) { return q < 3 && fin[q < 3 ? q : 0]; };
+            auto starts = [&](int q) { return q < 3 ? !fin[q] : !fin[2]; };
+            auto stage256 = [&](int k, int j) {
+                float(&mF)[CS] = u0, (&mS)[CS] = u1, (&rS)[CS] = u2, (&rF)[CS] = u3;      // stages 0, 1: maxima
+                float(&dF)[CS] = u1, (&iS)[CS] = u2;                                      // from stage 1 on: den handed on, 1 / den
+                if (k == 0) {
+                    float f = NEG, s0 = NEG;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float mq = CHAIN_SX(j, 4 * q);
+#pragma unroll
+                        for (int s = 4 * q + 1; s < 4 * q + 4 && s < SP; ++s) mq = fmaxf(mq, CHAIN_SX(j, s));
+                        if (q < 3) f = finishes(q) ? fmaxf(f, mq) : f;
+                        s0 = starts(q) ? fmaxf(s0, mq) : s0;
+                    }
+                    mF[j] = f;
+                    mS[j] = s0;
+                    rS[j] = lane_fetch(a_prev, s0);
+                    rF[j] = lane_fetch(a_next, f);
+                } else if (k == 1) {
+                    const float xF = fmaxf(mF[j], rS[j]), xS = fmaxf(mS[j], rF[j]);      // maxima of point 3 + g, of point 4 + g
+#pragma unroll
+                    for (int s = 0; s < SP; s += 2) {
+                        const float mx = finishes(s >> 2) ? xF : xS;
+                        const f32x2 e2 = (f32x2{CHAIN_SX(j, s), CHAIN_SX(j, s + 1)} - f32x2{mx, mx}) * l2e;
+                        CHAIN_SX(j, s) = __builtin_amdgcn_exp2f(e2.x);
+                        CHAIN_SX(j, s + 1) = __builtin_amdgcn_exp2f(e2.y);
+                    }
+                    // den: the starting slots from 0, handed to the next lane group, which continues over its finishing slots
+                    float d = 0.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float t = d;
+#pragma unroll
+                        for (int s = 4 * q; s < 4 * q + 4 && s < SP; ++s) t = __fadd_rn(t, CHAIN_SX(j, s));
+                        d = starts(q) ? t : d;
+                    }
+                    dF[j] = lane_fetch(a_prev, d);
+                } else if (k == 2) {
+                    float d = dF[j];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        float t = d;
+#pragma unroll
+                        for (int s = 4 * q; s < 4 * q + 4; ++s) t = __fadd_rn(t, CHAIN_SX(j, s));
+                        d = finishes(q) ? t : d;
+                    }
+                    dF[j] = __fdiv_rn(1.0f, d);                            // 1 / den of point 3 + g (lane group 0: of nothing, never used)
+                    iS[j] = lane_fetch(a_next, dF[j]);                     // 1 / den of point 4 + g
+                } else if (k == 3) {
+#pragma unroll
+                    for (int s = 0; s < SP; s += 2) {
+                        const float iv = finishes(s >> 2) ? dF[j] : iS[j];
+                        const f32x2 w2 = f32x2{CHAIN_SX(j, s), CHAIN_SX(j, s + 1)} * f32x2{iv, iv};
+                        CHAIN_SX(j, s) = w2.x;
+                        CHAIN_SX(j, s + 1) = w2.y;
+                    }
+                    float o = 0.f;                                         // out of the starting slots
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float t = o;
+#pragma unroll
+                        for (int s = 4 * q; s < 4 * q + 4 && s < SP; ++s) t = __fmaf_rn(CHAIN_SX(j, s), CHAIN_ST(j, s), t);
+                        o = starts(q) ? t : o;
+                    }
+                    o_end[j] = lane_fetch(a_prev, o);
+                } else {
+                    float o = o_end[j];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        float t = o;
+#pragma unroll
+                        for (int s = 4 * q; s < 4 * q + 4; ++s) t = __fmaf_rn(CHAIN_SX(j, s), CHAIN_ST(j, s), t);
+                        o = finishes(q) ? t : o;
+                    }
+                    o_end[j] = o;
+                }
+            };
+            // d = 512: point 4's neighbours 4 g + e are lane group g's four spare slots, g = 0, 1, 2 (lane group 3's are idle, or carry
+            // a straddler's rows, which stay outside: they left for the scratch tensors above).  Every lane runs its four slots from
+            // what the previous lane group hands it, three times: after hop h lane group h holds the chain over the neighbours
+            // 0 .. 4 h + 3, so lane group 2 ends with the whole sum.
+            const int a_g0 = L.c16 * 4, a_g1 = (16 + L.c16) * 4, a_g2 = (32 + L.c16) * 4;      // same column, lane group 0 / 1 / 2
+            auto stage512 = [&](int k, int j) {
+                if (k == 0) {
+                    const float m = fmaxf(fmaxf(CHAIN_SX(j, 0), CHAIN_SX(j, 1)), fmaxf(CHAIN_SX(j, 2), CHAIN_SX(j, 3)));
+                    u0[j] = lane_fetch(a_g0, m);
+                    u1[j] = lane_fetch(a_g1, m);
+                    u2[j] = lane_fetch(a_g2, m);
+                } else if (k == 1 || k == 2 || k == 3) {
+                    if (k == 1) {
+                        const float mx = fmaxf(fmaxf(u0[j], u1[j]), u2[j]);
+#pragma unroll
+                        for (int s = 0; s < 4; s += 2) {
+                            const f32x2 e2 = (f32x2{CHAIN_SX(j, s), CHAIN_SX(j, s + 1)} - f32x2{mx, mx}) * l2e;
+                            CHAIN_SX(j, s) = __builtin_amdgcn_exp2f(e2.x);
+                            CHAIN_SX(j, s + 1) = __builtin_amdgcn_exp2f(e2.y);
+                        }
+                    }
+                    float t = k == 1 ? 0.f : u0[j];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) t = __fadd_rn(t, CHAIN_SX(j, s));
+                    if (k < 3) u0[j] = lane_fetch(a_prev, t);
+                    else u0[j] = lane_fetch(a_g2, __fdiv_rn(1.0f, t));     // lane group 2's: 1 / den of point 4
+                } else {
+                    if (k == 4) {
+#pragma unroll
+                        for (int s = 0; s < 4; s += 2) {
+                            const f32x2 w2 = f32x2{CHAIN_SX(j, s), CHAIN_SX(j, s + 1)} * f32x2{u0[j], u0[j]};
+                            CHAIN_SX(j, s) = w2.x;
+                            CHAIN_SX(j, s + 1) = w2.y;
+                        }
+                    }
+                    float t = k == 4 ? 0.f : u1[j];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) t = __fmaf_rn(CHAIN_SX(j, s), CHAIN_ST(j, s), t);
+                    o_end[j] = t;
+                    if (k < 6) u1[j] = lane_fetch(a_prev, t);
+                }
+            };
+#pragma unroll
+            for (int i = 0; i < (NST > NH ? NST : NH); ++i) {
+                if (i < NST) {
+#pragma unroll
+                    for (int j = 0; j < CS; ++j) {
+                        if constexpr (NUA == 3) stage256(i, j);
+                        else stage512(i, j);
+                    }
+                }
+                CHAIN_TACC(t_spare);
+                __builtin_amdgcn_sched_barrier(0);
+                if (i < NH) {
+                    if (i & 1) own_second(i >> 1);
+                    else own_first(i >> 1);
+                }
+                CHAIN_TACC(t_own);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // the lane group where a spare point's chains end stores its row: d = 256 lane group g >= 1 point 3 + g, d = 512 lane group 2 point 4
+            const int st_pt = NUA == 3 ? 3 + L.g : 4;
+            if ((NUA == 3 ? L.g > 0 : L.g == 2) && st_pt < npts) {
+#pragma unroll
+                for (int j = 0; j < CS; ++j) {
+                    if (a.res_split) chain_store_split_nt(a.res, pt0 + st_pt, D, L.col[j], o_end[j]);
+                    else __builtin_nontemporal_store(o_end[j], &a.res[(pt0 + st_pt) * D + L.col[j]]);
                 }
             }
+            CHAIN_TACC(t_spare);
+#undef CHAIN_SX
+#undef CHAIN_ST
         }
+        CHAIN_STAMP_END();
     }
 }
 
-template <int D, int KK, bool O32>
+// TRIM (a.trim; SAPCU_CHAIN_TRIM=0 turns it off for a handle): the spare-slot sums handed from lane group to lane group and (d = 256)
+// fc_delta on the exact-f32 MFMA, instead of the four-fold sums over fetched values and the VALU fc_delta.  Same bits either way.
+template <int D, int KK, bool O32, bool TRIM>
 __global__ __launch_bounds__(ChainShape<D>::NW * 64, (D == 128 ? SAPCU_CHAIN_LB128 : 1)) void fn_edge_chain_kernel(const ChainArgs a) {
-    fn_edge_chain_body<D, KK, O32, false>(a);
+    fn_edge_chain_body<D, KK, O32, false, TRIM>(a);
 }
 
 // d = 512, kk = 12 with filled groups (a.fill_x / a.fill_t)
-template <bool O32>
+template <bool O32, bool TRIM>
 __global__ __launch_bounds__(ChainShape<512>::NW * 64, 1) void fn_edge_chain_fill_kernel(const ChainArgs a) {
-    fn_edge_chain_body<512, 12, O32, true>(a);
+    fn_edge_chain_body<512, 12, O32, true, TRIM>(a);
 }
 
 // The straddlers of the filled groups: one thread per (straddler, column) reads its 12 scaled logits and 12 t = v_j + pe in neighbour
@@ -670,30 +988,36 @@ __global__ __launch_bounds__(256) void fn_chain_straddler_kernel(const float* __
     else __builtin_nontemporal_store(out, &res[pt * d + col]);
 }
 
-template <int D, int KK, bool O32>
+template <int D, int KK, bool O32, bool TRIM>
 static int launch_chain_t(const ChainArgs& a, hipStream_t st) {
     constexpr int lds = ChainShape<D>::LDS;
     static DeviceOnce lds_once;                         // one per kernel instantiation, one bit per device
-    SAPCU_SET_MAX_LDS(lds_once, (&fn_edge_chain_kernel<D, KK, O32>), lds);
+    SAPCU_SET_MAX_LDS(lds_once, (&fn_edge_chain_kernel<D, KK, O32, TRIM>), lds);
     constexpr int PPG = ChainSlots<D, KK>::PPG;
     const int64_t ngroups = (a.P + PPG - 1) / PPG;
     const int64_t grid = ngroups < 8 ? ngroups : ((ngroups + 7) / 8) * 8;      // 8 XCD ranges of equal slot count
     SAPCU_CHECK_ARG(grid < 0x7fffffffLL, "edge_chain: too many groups");
-    hipLaunchKernelGGL((fn_edge_chain_kernel<D, KK, O32>), dim3((unsigned)grid), dim3(ChainShape<D>::NW * 64), lds, st, a);
+    hipLaunchKernelGGL((fn_edge_chain_kernel<D, KK, O32, TRIM>), dim3((unsigned)grid), dim3(ChainShape<D>::NW * 64), lds, st, a);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
 }
 
-template <bool O32>
+template <int D, int KK>
+static int launch_chain_plain(const ChainArgs& a, bool o32, hipStream_t st) {
+    if (a.trim) return o32 ? launch_chain_t<D, KK, true, true>(a, st) : launch_chain_t<D, KK, false, true>(a, st);
+    return o32 ? launch_chain_t<D, KK, true, false>(a, st) : launch_chain_t<D, KK, false, false>(a, st);
+}
+
+template <bool O32, bool TRIM>
 static int launch_chain_fill_t(const ChainArgs& a, hipStream_t st) {
     constexpr int lds = ChainShape<512>::LDS, PPG = ChainSlots<512, 12>::PPG;
     static DeviceOnce lds_once;
-    SAPCU_SET_MAX_LDS(lds_once, (&fn_edge_chain_fill_kernel<O32>), lds);
+    SAPCU_SET_MAX_LDS(lds_once, (&fn_edge_chain_fill_kernel<O32, TRIM>), lds);
     const int64_t nsuper = a.P / 16;
     const int64_t ngroups = 3 * nsuper + (a.P - 16 * nsuper + PPG - 1) / PPG;
     const int64_t grid = ngroups < 8 ? ngroups : ((ngroups + 7) / 8) * 8;
     SAPCU_CHECK_ARG(grid < 0x7fffffffLL, "edge_chain: too many groups");
-    hipLaunchKernelGGL((fn_edge_chain_fill_kernel<O32>), dim3((unsigned)grid), dim3(ChainShape<512>::NW * 64), lds, st, a);
+    hipLaunchKernelGGL((fn_edge_chain_fill_kernel<O32, TRIM>), dim3((unsigned)grid), dim3(ChainShape<512>::NW * 64), lds, st, a);
     SAPCU_CHECK_LAUNCH();
     hipLaunchKernelGGL((fn_chain_straddler_kernel<12>), dim3((unsigned)((nsuper * 512 + 255) / 256)), dim3(256), 0, st, a.fill_x, a.fill_t,
                        nsuper, 512, a.res, a.res_split);
@@ -715,11 +1039,14 @@ int launch_fn_edge_chain(ChainArgs a, const float* patch, const int32_t* idx, in
     a.pd = pd;
     // (rows x row pitch + the three column ranges) in bytes below 4 GiB: 32-bit gather offsets
     const bool o32 = !a.wide_offsets && (uint64_t)a.P * (uint64_t)a.ldq * 4u + 3u * (uint64_t)d * 4u < (1ull << 32) && a.ldq > 0;
-    if (d == 128) return o32 ? launch_chain_t<128, 24, true>(a, st) : launch_chain_t<128, 24, false>(a, st);
-    if (d == 256) return o32 ? launch_chain_t<256, 18, true>(a, st) : launch_chain_t<256, 18, false>(a, st);
+    if (d == 128) return launch_chain_plain<128, 24>(a, o32, st);
+    if (d == 256) return launch_chain_plain<256, 18>(a, o32, st);
     // filled groups: the caller gave the two scratch areas ([P / 16][12][512] floats each) and there is at least one super-group
-    if (a.fill_x && a.fill_t && a.P >= 16) return o32 ? launch_chain_fill_t<true>(a, st) : launch_chain_fill_t<false>(a, st);
-    return o32 ? launch_chain_t<512, 12, true>(a, st) : launch_chain_t<512, 12, false>(a, st);
+    if (a.fill_x && a.fill_t && a.P >= 16) {
+        if (a.trim) return o32 ? launch_chain_fill_t<true, true>(a, st) : launch_chain_fill_t<false, true>(a, st);
+        return o32 ? launch_chain_fill_t<true, false>(a, st) : launch_chain_fill_t<false, false>(a, st);
+    }
+    return launch_chain_plain<512, 12>(a, o32, st);
 }
 
 int launch_pack_chain_weights(const void* w16_hi, const void* w16_lo, int d, void* out, hipStream_t st) {

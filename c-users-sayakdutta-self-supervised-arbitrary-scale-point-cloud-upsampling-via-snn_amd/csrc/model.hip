@@ -100,6 +100,7 @@ struct sapcu_model {
     bool opt_chain = true;            // SAPCU_CHAIN=0: fn blocks as the five-kernel edge chain
     bool opt_chain_wide = false;      // SAPCU_CHAIN=wide: the fused chain with 64-bit gather addresses (the form tensors >= 4 GiB take)
     bool opt_chain_fill = true;       // SAPCU_CHAIN_FILL=0: the d = 512 fused chain in plain groups of five points, four slots of 64 idle
+    bool opt_chain_trim = true;       // SAPCU_CHAIN_TRIM=0: the fused chain's fc_delta on the VALU and its spare-slot points summed in every lane group
     bool opt_shortk = true;           // SAPCU_SHORTK=0: fc1 / conv_final on gemm_sf16_kernel instead of gemm_shortk.hip
     bool opt_fn_maxfuse = true;       // SAPCU_FN_MAXFUSE=0: conv_final GEMM + rowgroup_max
     bool opt_fn_fold_out = true;      // SAPCU_FN_FOLD_OUT=0: fn blocks end with out_proj and fc2 as two GEMMs instead of the folded one
@@ -168,6 +169,7 @@ static void read_env_switches(sapcu_model* m) {
     m->opt_chain = !env_is("SAPCU_CHAIN", "0");
     m->opt_chain_wide = env_is("SAPCU_CHAIN", "wide");
     m->opt_chain_fill = !env_is("SAPCU_CHAIN_FILL", "0");
+    m->opt_chain_trim = !env_is("SAPCU_CHAIN_TRIM", "0");
     m->opt_shortk = !env_is("SAPCU_SHORTK", "0");
     m->opt_fn_maxfuse = !env_is("SAPCU_FN_MAXFUSE", "0");
     m->opt_fn_fold_out = !env_is("SAPCU_FN_FOLD_OUT", "0");
@@ -377,6 +379,7 @@ static int fn_edge_chain_fused(const sapcu_model* m, const FnWs& W, const FnEdge
     ca.w3p = cw + chain_w_off(e.l, 2); ca.b3 = m->p(sb + B_GAMMA2_B);
     ca.inv_sqrt_hd = 1.0f / e.sqrt_hd;
     ca.res = W.RES; ca.res_split = e.SP; ca.T = 4; ca.wide_offsets = m->opt_chain_wide ? 1 : 0;
+    ca.trim = m->opt_chain_trim ? 1 : 0;
     // d = 512, filled groups: the straddlers' logits go to W.X (consumed by the q|k|v GEMM, not written again before the chain has
     // run) and their t = v_j + pe to W.B1 (unused between the last unfused chain and conv_final) — where both hold
     // [P / 16][12][512] floats; else the plain grouping
@@ -1034,6 +1037,17 @@ int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t poin
     ca.w3p = W.packed[2]; ca.b3 = b3;
     ca.inv_sqrt_hd = 1.0f / (float)sqrt((double)(d / heads));
     ca.res = res_out; ca.res_split = 0; ca.T = lif_steps;
+    ca.trim = 1;
+#ifdef CHAIN_STAMPS
+    // diagnostic build (profiles/chain_stamps.py): the stamps go behind what the entry needs, where the caller's workspace has the room
+    // (16 slots of 8 bytes per group, at most points / 4 + 1 groups), and SAPCU_CHAIN_TRIM=0 is honoured at every call
+    {
+        const int64_t sbytes = (points / 4 + 1) * 16 * 8;
+        const int64_t off = (need + 255) / 256 * 256;
+        if (workspace_bytes >= off + sbytes + 256) ca.stamps = (unsigned long long*)((char*)ws_align256(workspace) + off);
+        if (env_is("SAPCU_CHAIN_TRIM", "0")) ca.trim = 0;
+    }
+#endif
     return launch_fn_edge_chain(ca, patch, idx, d, kk, W.tab, W.pd, st);
 }
 

@@ -44,6 +44,10 @@ struct ChainArgs {
     int wide_offsets;          // 1: 64-bit gather addresses even where 32-bit byte offsets would do (SAPCU_CHAIN=wide; parity tests)
     float* fill_x;             // d = 512: scratch [P / 16][12][512] each for the filled grouping (fn_edge_chain.hip), dead before and after
     float* fill_t;             // the launch; null: the plain groups of five points
+    int trim;                  // 1: fc_delta on the exact-f32 MFMA, spare-slot sums handed from lane group to lane group (SAPCU_CHAIN_TRIM)
+#ifdef CHAIN_STAMPS
+    unsigned long long* stamps;      // diagnostic build: [groups][16] phase stamps (fn_edge_chain.hip), or null
+#endif
 };
 bool fn_edge_chain_ok(int d, int kk);
 int launch_fn_edge_chain(ChainArgs a, const float* patch, const int32_t* idx, int d, int kk, int2* tab_ws, float4* pd_ws,

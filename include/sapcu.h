@@ -276,6 +276,8 @@ int sapcu_patch_knn(const float* feat, int64_t b, int m, int c, int ld, int k, i
  * parity / ablation switches SAPCU_BT, SAPCU_CHAIN (= 0, or "wide"), SAPCU_FN_MAXFUSE, SAPCU_FD_MAXFUSE, SAPCU_FD_SPLIT, SAPCU_FD_FUSED = 0, and
  * SAPCU_FN_FOLD_OUT = 0: fn blocks end with out_proj and fc2 as two GEMMs instead of the one folded at create, results equal to rounding;
  * SAPCU_CHAIN_FILL = 0: fn block 3's fused edge chain in plain groups of five points instead of super-groups of 16, bit-identical;
+ * SAPCU_CHAIN_TRIM = 0: the fused edge chain's epilogues in their earlier form (every lane group sums the points in spare slots over
+ * fetched copies; fc_delta of block 2 on the VALU), bit-identical;
  * SAPCU_SHORTK = 0: fn's fc1 and conv_final layers on the general f32-A split-f16 kernel instead of the short-K one, bit-identical —
  * sapcu_gemm_f32, which has no handle, reads this one switch at each call) are
  * read HERE, once; a forward never reads the environment.  Forwards of one handle (or of several) may run concurrently on
