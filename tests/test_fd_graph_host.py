@@ -1,8 +1,11 @@
-"""fd's graphed training step (row f-5), the part that needs no GPU: the fifth export table against include/sapcu_train_step.h,
-sapcu_multi_select's refusals before any launch, and what fd_trainer.GraphedTrainStep refuses before it captures anything."""
+"""The graphed training step (rows f-4 and f-5), the part that needs no GPU: the fifth export table against
+include/sapcu_train_step.h, sapcu_multi_select's refusals before any launch, what train_step.GraphedTrainStep — one class under the
+names fn_trainer.GraphedTrainStep and fd_trainer.GraphedTrainStep — refuses before it captures anything, and that it knows no network."""
 import ctypes
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -104,3 +107,31 @@ def test_the_graphed_step_is_one_method_under_two_names_and_no_counter_exists_be
         with pytest.raises((RuntimeError, AssertionError)):                       # the counter is a device tensor: no device, no counter
             fd_train.bad_index_counter("cuda:0")
         assert fd_train._BAD == {}
+
+
+def test_the_two_public_names_are_one_class_and_it_refuses_for_an_fn_trainer_too():
+    from sapcu_amd import fd_trainer, fn_trainer, train_step
+    assert fn_trainer.GraphedTrainStep is fd_trainer.GraphedTrainStep is train_step.GraphedTrainStep
+    assert fn_trainer.run_epoch is train_step.run_epoch and fn_trainer.clamp_neuron_parameters is train_step.clamp_neuron_parameters
+    cpu_model = torch.nn.Linear(3, 1)
+    batch = {"input": torch.zeros(1, 2, 4, 3), "normal": torch.zeros(1, 2, 3)}
+    for opt_kw, tr_kw, word in ((dict(capturable=True), dict(use_amp=True, scaler=object()), "GradScaler"),
+                                (dict(capturable=True), dict(gradient_accumulation=2), "accumulation"), (dict(), dict(), "capturable"),
+                                (dict(capturable=True), dict(), "ROCm")):
+        opt = torch.optim.AdamW(cpu_model.parameters(), lr=1e-3, **opt_kw)
+        with pytest.raises(ValueError, match=word):
+            fn_trainer.GraphedTrainStep(fn_trainer.Trainer(cpu_model, opt, **tr_kw), batch, warmup=0)
+    # the order, on a stub that has fn's attributes and would fail at the first use of a hook
+    tr = _StubTrainer(cpu_model, scaler=object(), gradient_accumulation=2, capturable=False)
+    tr.use_amp = True
+    with pytest.raises(ValueError, match="GradScaler"):
+        fn_trainer.GraphedTrainStep(tr, batch, warmup=0)
+    assert tr.batched == 0
+
+
+def test_train_step_does_not_import_fd_train():
+    """The shared module knows no network: importing it in a fresh interpreter loads neither fd_train nor a trainer."""
+    code = ("import sys, sapcu_amd.train_step\n"
+            "print(sorted(m for m in ('sapcu_amd.fd_train', 'sapcu_amd.fd_trainer', 'sapcu_amd.fn_trainer') if m in sys.modules))")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and r.stdout.strip() == "[]", (r.stdout, r.stderr[-2000:])
