@@ -129,6 +129,14 @@ _TRAIN_STEP_SIGNATURES = {
 }
 TRAIN_STEP_EXPORTS = tuple(_TRAIN_STEP_SIGNATURES)
 
+# include/sapcu_metrics.h: the nearest neighbour of every query in another cloud on the device cell grid (a sixth table)
+_METRICS_SIGNATURES = {
+    "sapcu_nn_cross_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "sapcu_nn_cross_grid_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_int64,
+                                        POINTER(c_int64), c_void_p]),
+}
+METRICS_EXPORTS = tuple(_METRICS_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -151,7 +159,7 @@ def load(path=None):
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
-            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

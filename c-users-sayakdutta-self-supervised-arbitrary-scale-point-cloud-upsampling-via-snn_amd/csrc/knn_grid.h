@@ -61,6 +61,8 @@ __device__ __forceinline__ int grid_coord(double v, double o, double h, int g) {
 }
 
 int launch_exclusive_scan_int(int* a, int64_t m, int* tile_sums, hipStream_t st);
+int launch_grid_bbox(const double* pts, int64_t n, double* partials, hipStream_t st);
+int launch_grid_params(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, hipStream_t st);
 int launch_grid_setup(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, GridParams* hp, hipStream_t st);
 int launch_grid_sort(const double* pts, int64_t n, const GridWs& w, const GridParams& hp, hipStream_t st);
 

@@ -332,12 +332,26 @@ int launch_exclusive_scan_int(int* a, int64_t m, int* tile_sums, hipStream_t st)
     return SAPCU_OK;
 }
 
-// the grid's parameters on the device and in *hp (one stream sync); hp->fallback: nothing else may be built
-int launch_grid_setup(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, GridParams* hp, hipStream_t st) {
-    hipLaunchKernelGGL(grid_bbox_kernel, dim3(KNN_GRID_BBOX_BLOCKS), dim3(256), 0, st, pts, n, w.partials);
+// the bounding-box partials of any point array: [KNN_GRID_BBOX_BLOCKS][8] = min xyz, max xyz, bad flag
+int launch_grid_bbox(const double* pts, int64_t n, double* partials, hipStream_t st) {
+    hipLaunchKernelGGL(grid_bbox_kernel, dim3(KNN_GRID_BBOX_BLOCKS), dim3(256), 0, st, pts, n, partials);
     SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+// the grid's parameters on the device only (w.params), nothing read back
+int launch_grid_params(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, hipStream_t st) {
+    const int rc = launch_grid_bbox(pts, n, w.partials, st);
+    if (rc != SAPCU_OK) return rc;
     hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(64), 0, st, w.partials, k, n, cell_size, grid_cell_cap(n), w.params);
     SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+// the grid's parameters on the device and in *hp (one stream sync); hp->fallback: nothing else may be built
+int launch_grid_setup(const double* pts, int64_t n, int k, double cell_size, const GridWs& w, GridParams* hp, hipStream_t st) {
+    const int rc = launch_grid_params(pts, n, k, cell_size, w, st);
+    if (rc != SAPCU_OK) return rc;
     SAPCU_CHECK_HIP(hipMemcpyAsync(hp, w.params, sizeof(*hp), hipMemcpyDeviceToHost, st));
     SAPCU_CHECK_HIP(hipStreamSynchronize(st));
     return SAPCU_OK;

@@ -1,0 +1,267 @@
+// Exact nearest neighbour of every query in ANOTHER cloud on the cell grid of knn_grid.hip: the distance vectors behind Chamfer,
+// Hausdorff, precision / recall and F-score (sapcu_amd/metrics.py).  Replaces the two sklearn NearestNeighbors(n_neighbors=1)
+// queries per cloud pair of the reference's external/Meta-PU_evaluation/evaluation_code/evaluation_cd.py.
+//
+// nn_cross_kernel, one query per lane:
+//   * the grid is built over the cloud by knn_grid.hip's launchers (bounding box, counting sort into the cell-ordered SoA copy);
+//   * the queries are counting-sorted by the (clamped) cell of the CLOUD's grid they fall in, with the same launchers;
+//   * a cell with c queries gets ceil(c / 64) wavefronts: the exclusive scan of those counts is searched by wave w (binary search)
+//     for its (cell, chunk); the launch is the upper bound ceil(nq / 64) + min(cells, nq) waves, the ones beyond the total exit;
+//   * all lanes of a wave share one cell, so the Chebyshev-shell walk of knn_self_grid_kernel, its ranges start[..] and its loop
+//     bounds are wave-uniform.  A range is read 64 points at a time, coalesced, into the wave's own LDS slab; every point is then
+//     read back by all lanes at once (one address: an LDS broadcast) and tested against each lane's own query.  A lane keeps
+//     (best d, best index) in registers and compares on the key (d, index): candidates arrive in cell order;
+//   * the squared distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 operations, the output sqrt_cr of it,
+//     the lowest index among equal distances: bit for bit knn_outer.hip at k = 1;
+//   * after shell r each lane evaluates the stop rule of knn_self_grid_kernel for its own position (face distance less slack,
+//     squared, shrunk by 1 - 1e-9, STRICTLY above its best); the wave leaves when every lane is satisfied.  A lane that was
+//     satisfied earlier goes on computing: a minimum over more candidates is still the minimum;
+//   * the slack covers the queries as well: GridParams.slack is sized to the cloud's coordinates, and a query 1e6 extents outside
+//     the box rounds q - face far above it.  nn_cross_setup_kernel adds 1e-11 * (largest |coordinate| of the queries' bounding box).
+//     The clamped cell of an outside query needs nothing more: a face plane still bounds everything beyond it from below, and a
+//     side at the grid's edge has nothing beyond it;
+//   * results go to the queries' original positions with ordinary vector stores.  No float atomics, no scratch.
+// Non-finite or huge (|x| > 1e150) coordinates in either set, and n < KNN_GRID_MIN_N with the automatic cell size, run the
+// brute-force kernel of knn_outer.hip instead.
+#include "common.h"
+#include "knn_grid.h"
+#include "../../include/sapcu_metrics.h"
+
+namespace sapcu {
+
+// automatic cell edge: emax * sqrt(2 * NN_CROSS_CELL_POP / n), about 2 * NN_CROSS_CELL_POP points in an occupied cell of a surface
+// (profiles/metrics_nn.txt: the sweep over 8, 16, 32, 64)
+constexpr int NN_CROSS_CELL_POP = 16;
+constexpr int NN_CROSS_WAVES = 4;
+
+struct CrossWs {
+    GridWs g;                // the cloud's grid
+    GridWs q;                // the queries in the cloud's cells (q.params = g.params; q.partials = their own bounding box)
+    int* wstart;             // [cells + 1]: wavefronts per cell, then exclusive prefix sums
+    int64_t* brute_idx;      // [nq] indices of the brute-force route when the caller wants none (shares q.sx: no grid then)
+    size_t bytes;
+};
+
+static CrossWs cross_ws_layout(void* base, int64_t n, int64_t nq) {
+    const int64_t cap = grid_cell_cap(n);
+    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    CrossWs w;
+    w.g = grid_ws_layout(base, n);
+    WsCarver c(base ? (char*)base + w.g.bytes : nullptr);
+    w.q.partials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
+    w.q.params = w.g.params;
+    w.q.start = c.take<int>(cap + 1);
+    w.q.cursor = c.take<int>(cap);
+    w.q.tile_sums = c.take<int>(tiles);
+    w.q.key = c.take<int>(nq);
+    w.q.sx = c.take<double>(nq);
+    w.q.sy = c.take<double>(nq);
+    w.q.sz = c.take<double>(nq);
+    w.q.sidx = c.take<int>(nq);
+    w.wstart = c.take<int>(cap + 1);
+    w.brute_idx = (int64_t*)w.q.sx;
+    w.q.bytes = c.bytes();
+    w.bytes = w.g.bytes + c.bytes();
+    return w;
+}
+
+// one thread: the queries' bad flag and magnitude into the cloud's grid parameters
+__global__ void nn_cross_setup_kernel(const double* __restrict__ qpartials, GridParams* __restrict__ prm) {
+    if (threadIdx.x != 0) return;
+    double amax = 0.0, bad = 0.0;
+    for (int b = 0; b < KNN_GRID_BBOX_BLOCKS; ++b) {
+        const double* q = qpartials + b * 8;
+        bad = fmax(bad, q[6]);
+        for (int c = 0; c < 6; ++c)
+            if (fabs(q[c]) <= 1e150) amax = fmax(amax, fabs(q[c]));        // a block without points holds +-inf
+    }
+    if (bad != 0.0) {
+        prm->fallback = 1;
+        return;
+    }
+    prm->slack = __dadd_rn(prm->slack, __dmul_rn(1e-11, amax));
+}
+
+// wavefronts per cell: ceil(queries / 64); entry `cells` (the scan's total) starts at 0
+__global__ __launch_bounds__(256) void nn_cross_waves_kernel(const int* __restrict__ qstart, int64_t cells, int* __restrict__ wstart) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > cells) return;
+    wstart[c] = c < cells ? (qstart[c + 1] - qstart[c] + 63) >> 6 : 0;
+}
+
+struct __align__(16) CrossPt {
+    double x, y, z;
+    int idx, pad;
+};
+
+struct CrossBest {
+    double d;
+    int i;
+};
+
+// every point of the sorted range [a, b) against every lane's query
+__device__ __forceinline__ void cross_scan_range(CrossBest& B, int a, int b, double qx, double qy, double qz,
+                                                 const double* __restrict__ sx, const double* __restrict__ sy,
+                                                 const double* __restrict__ sz, const int* __restrict__ sidx, CrossPt* slab, int lane) {
+    for (int off = a; off < b; off += 64) {
+        const int j = off + lane;
+        CrossPt mine{0.0, 0.0, 0.0, 0x7fffffff, 0};
+        if (j < b) {
+            mine.x = sx[j];
+            mine.y = sy[j];
+            mine.z = sz[j];
+            mine.idx = sidx[j];
+        }
+        __builtin_amdgcn_wave_barrier();
+        slab[lane] = mine;
+        __builtin_amdgcn_wave_barrier();
+        const int cnt = min(64, b - off);                                   // wave-uniform
+#pragma unroll 4
+        for (int t = 0; t < cnt; ++t) {
+            const CrossPt p = slab[t];                                      // one address for the whole wave: a broadcast
+            const double dx = __dsub_rn(qx, p.x);
+            const double dy = __dsub_rn(qy, p.y);
+            const double dz = __dsub_rn(qz, p.z);
+            double d = __dmul_rn(dx, dx);
+            d = __dadd_rn(d, __dmul_rn(dy, dy));
+            d = __dadd_rn(d, __dmul_rn(dz, dz));
+            if (d < B.d || (d == B.d && p.idx < B.i)) {
+                B.d = d;
+                B.i = p.idx;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void nn_cross_kernel(const GridParams* __restrict__ prm, const int* __restrict__ start,
+                                                       const double* __restrict__ sx, const double* __restrict__ sy,
+                                                       const double* __restrict__ sz, const int* __restrict__ sidx,
+                                                       const int* __restrict__ qstart, const int* __restrict__ wstart,
+                                                       const double* __restrict__ qsx, const double* __restrict__ qsy,
+                                                       const double* __restrict__ qsz, const int* __restrict__ qsidx, int cells,
+                                                       double* __restrict__ dist_out, int64_t* __restrict__ idx_out) {
+    __shared__ CrossPt slabs[NN_CROSS_WAVES][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t w = (int64_t)blockIdx.x * NN_CROSS_WAVES + wave;
+    if (w >= (int64_t)wstart[cells]) return;                               // wave-uniform: beyond the last (cell, chunk)
+    int lo = 0, hi = cells;                                                 // wstart[lo] <= w < wstart[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)wstart[mid] <= w) lo = mid; else hi = mid;
+    }
+    const int cell = lo;
+    const int qa = qstart[cell] + ((int)w - wstart[cell]) * 64, qb = qstart[cell + 1];
+    const bool valid = qa + lane < qb;
+    const int j = valid ? qa + lane : qa;                                   // a spare lane repeats the chunk's first query
+    const double qx = qsx[j], qy = qsy[j], qz = qsz[j];
+    const GridParams p = *prm;
+    const int cx = cell % p.gx, cy = (cell / p.gx) % p.gy, cz = cell / (p.gx * p.gy);
+    const double INF = __builtin_huge_val();
+    CrossBest B{INF, 0x7fffffff};
+    CrossPt* slab = slabs[wave];
+    const int rmax = max(max(p.gx, p.gy), p.gz);
+    for (int r = 0; r <= rmax; ++r) {
+        const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
+        const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
+        const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
+        for (int z = z0; z <= z1; ++z) {
+            for (int y = y0; y <= y1; ++y) {
+                const int row = (z * p.gy + y) * p.gx;
+                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {        // a face row of the shell: its whole x range
+                    cross_scan_range(B, start[row + x0], start[row + x1 + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
+                } else {                                                            // an inner row: its two end cells
+                    if (cx - r >= 0)
+                        cross_scan_range(B, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
+                    if (cx + r < p.gx)
+                        cross_scan_range(B, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
+                }
+            }
+        }
+        // each lane's lower bound for every point outside the visited block [c-r, c+r]^3 (a side at the grid's edge has none)
+        double bnd = INF;
+        if (cx - r > 0) bnd = fmin(bnd, __dsub_rn(qx, __dadd_rn(p.ox, __dmul_rn((double)(cx - r), p.h))));
+        if (cx + r < p.gx - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.ox, __dmul_rn((double)(cx + r + 1), p.h)), qx));
+        if (cy - r > 0) bnd = fmin(bnd, __dsub_rn(qy, __dadd_rn(p.oy, __dmul_rn((double)(cy - r), p.h))));
+        if (cy + r < p.gy - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oy, __dmul_rn((double)(cy + r + 1), p.h)), qy));
+        if (cz - r > 0) bnd = fmin(bnd, __dsub_rn(qz, __dadd_rn(p.oz, __dmul_rn((double)(cz - r), p.h))));
+        if (cz + r < p.gz - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oz, __dmul_rn((double)(cz + r + 1), p.h)), qz));
+        if (cx - r <= 0 && cx + r >= p.gx - 1 && cy - r <= 0 && cy + r >= p.gy - 1 && cz - r <= 0 && cz + r >= p.gz - 1)
+            break;                                                           // the whole grid is visited (wave-uniform)
+        bnd = __dsub_rn(bnd, p.slack);
+        const bool open = !(bnd > 0.0 && __dmul_rn(__dmul_rn(bnd, bnd), 1.0 - 1e-9) > B.d);
+        if (__ballot(open) == 0ull) break;                                   // every lane's bound is strictly above its best
+    }
+    if (valid) {
+        const int o = qsidx[j];
+        dist_out[o] = sqrt_cr(B.d);
+        if (idx_out) idx_out[o] = B.i;
+    }
+}
+
+int launch_nn_cross(const double* cloud, int64_t n, const double* queries, int64_t nq, double cell_size, double* dist, int64_t* idx,
+                    void* ws, int64_t* info, hipStream_t st) {
+    if (info) info[0] = info[1] = info[2] = info[3] = 0;
+    if (nq == 0) return SAPCU_OK;
+    const CrossWs w = cross_ws_layout(ws, n, nq);
+    int64_t* bidx = idx ? idx : w.brute_idx;
+    if (cell_size == 0.0 && n < KNN_GRID_MIN_N) return launch_knn_outer(cloud, n, queries, nq, 1, bidx, dist, nullptr, st);
+    int rc = launch_grid_params(cloud, n, NN_CROSS_CELL_POP, cell_size, w.g, st);
+    if (rc != SAPCU_OK) return rc;
+    rc = launch_grid_bbox(queries, nq, w.q.partials, st);
+    if (rc != SAPCU_OK) return rc;
+    hipLaunchKernelGGL(nn_cross_setup_kernel, dim3(1), dim3(64), 0, st, w.q.partials, w.g.params);
+    SAPCU_CHECK_LAUNCH();
+    GridParams hp;
+    SAPCU_CHECK_HIP(hipMemcpyAsync(&hp, w.g.params, sizeof(hp), hipMemcpyDeviceToHost, st));
+    SAPCU_CHECK_HIP(hipStreamSynchronize(st));
+    if (hp.fallback) return launch_knn_outer(cloud, n, queries, nq, 1, bidx, dist, nullptr, st);
+    if (info) {
+        info[0] = 1;
+        info[1] = hp.gx;
+        info[2] = hp.gy;
+        info[3] = hp.gz;
+    }
+    rc = launch_grid_sort(cloud, n, w.g, hp, st);
+    if (rc != SAPCU_OK) return rc;
+    rc = launch_grid_sort(queries, nq, w.q, hp, st);                        // the cloud's parameters: the cloud's cells
+    if (rc != SAPCU_OK) return rc;
+    const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
+    hipLaunchKernelGGL(nn_cross_waves_kernel, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, st, w.q.start, cells, w.wstart);
+    SAPCU_CHECK_LAUNCH();
+    rc = launch_exclusive_scan_int(w.wstart, cells + 1, w.q.tile_sums, st);
+    if (rc != SAPCU_OK) return rc;
+    const int64_t waves = (nq + 63) / 64 + (cells < nq ? cells : nq);       // >= sum of ceil(count / 64): nothing is read back
+    const int64_t grid = (waves + NN_CROSS_WAVES - 1) / NN_CROSS_WAVES;
+    hipLaunchKernelGGL(nn_cross_kernel, dim3((unsigned)grid), dim3(256), 0, st, w.g.params, w.g.start, w.g.sx, w.g.sy, w.g.sz, w.g.sidx,
+                       w.q.start, w.wstart, w.q.sx, w.q.sy, w.q.sz, w.q.sidx, (int)cells, dist, idx);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+}  // namespace sapcu
+
+// ================================================================================== C ABI
+using namespace sapcu;
+
+extern "C" {
+
+int64_t sapcu_nn_cross_workspace_bytes(int64_t n, int64_t nq) {
+    if (n < 1 || n > (1LL << 29) || nq < 0 || nq > (1LL << 31) - 64) return -1;
+    return (int64_t)cross_ws_layout(nullptr, n, nq).bytes;
+}
+
+int sapcu_nn_cross_grid_f64(const double* cloud, int64_t n, const double* queries, int64_t nq, double cell_size, double* dist_out,
+                            int64_t* idx_out, void* workspace, int64_t workspace_bytes, int64_t* info_host, void* stream) {
+    SAPCU_CHECK_ARG(n >= 1 && n <= (1LL << 29), "nn_cross_grid: need 1 <= n <= 2^29 (n=%lld)", (long long)n);
+    SAPCU_CHECK_ARG(nq >= 0 && nq <= (1LL << 31) - 64, "nn_cross_grid: need 0 <= nq <= 2^31 - 64 (nq=%lld)", (long long)nq);
+    SAPCU_CHECK_ARG(cloud && ((queries && dist_out) || nq == 0), "nn_cross_grid: null pointer");      // no query: nothing is written
+    SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "nn_cross_grid: cell_size must be finite and >= 0");
+    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "nn_cross_grid: the workspace must be 8-byte aligned (f64 tables)");
+    const int64_t need = (int64_t)cross_ws_layout(nullptr, n, nq).bytes;
+    SAPCU_CHECK_ARG(workspace && workspace_bytes >= need, "nn_cross_grid: workspace of %lld bytes, need %lld",
+                    (long long)workspace_bytes, (long long)need);
+    return launch_nn_cross(cloud, n, queries, nq, cell_size, dist_out, idx_out, workspace, info_host, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -76,3 +76,12 @@ def process_file(input_path, output_path, generator, target_points):
     """generate.py:81-101: text cloud in, ``target_points`` upsampled points out ("%.6f")."""
     cloud = np.loadtxt(input_path)
     np.savetxt(output_path, process_cloud(cloud, generator, target_points), fmt="%.6f")
+
+
+def evaluate_file(pred_path, gt_path, device="cuda"):
+    """Chamfer, Hausdorff, precision / recall and F-score of two text clouds (``metrics.cloud_metrics``), loaded the way
+    ``process_file`` loads its input; the reference scores such files on the host (evaluation_cd.py)."""
+    from . import metrics
+    pred, gt = np.loadtxt(pred_path, ndmin=2)[:, :3], np.loadtxt(gt_path, ndmin=2)[:, :3]
+    dev = torch.device(device)
+    return metrics.cloud_metrics(torch.from_numpy(np.ascontiguousarray(pred)).to(dev), torch.from_numpy(np.ascontiguousarray(gt)).to(dev))
