@@ -137,6 +137,14 @@ _METRICS_SIGNATURES = {
 }
 METRICS_EXPORTS = tuple(_METRICS_SIGNATURES)
 
+# include/sapcu_data.h: fd's and fn's training samples from raw cloud pairs (a seventh table)
+_DATA_SIGNATURES = {
+    "sapcu_train_patches_workspace_bytes": (c_int64, [c_int64]),
+    "sapcu_train_patches_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_void_p, c_int64, c_void_p]),
+}
+DATA_EXPORTS = tuple(_DATA_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -159,7 +167,8 @@ def load(path=None):
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
-            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
+            list(_DATA_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

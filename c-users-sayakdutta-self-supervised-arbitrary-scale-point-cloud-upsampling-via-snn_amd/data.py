@@ -1,0 +1,286 @@
+"""Training batches of fd and fn built on the device from raw cloud pairs.
+
+The reference builds a sample in ``Dataset.__getitem__`` on DataLoader workers with two ``scipy.spatial.cKDTree`` builds —
+``fd/datacore.py`` ``PU1KDataset`` (:91-149: augment, normalise by the input cloud, distance of every input point to the denser
+cloud, the k nearest input points of every input point) and ``fn/datacore.py`` ``PU1KMeshDataset`` (:201-258: the same on sampled
+mesh points with their face normals, 64 random centres).  Here the data set is uploaded once and a whole batch is one call of
+``sapcu_train_patches_f32`` (csrc/train_patches.hip, include/sapcu_data.h): three launches, no host read-back.  Given the same
+augmentation draws every output equals the reference's bit for bit, up to its BLAS rotation product.
+
+``PU1KPatches`` / ``MeshPatches`` are iterables of stacked batch dicts with the reference's keys; they plug into
+``train_step.run_epoch(trainer, loader)`` for ``fd_trainer`` / ``fn_trainer``.  The draws (angle, scale, jitter, centres, order) come
+from a device ``torch.Generator`` seeded by (seed, epoch, batch): deterministic, and not the reference's numpy stream.
+
+No CPU path: the HIP library and a device are required.
+"""
+import math
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_N, MAX_G, MAX_K = 4096, 65536, 128
+
+
+def clamp_k(k, n):
+    """The neighbour count of a cloud of n points: min(k, n), as the reference's ``min(self.k_neighbors, len(input_pc))``."""
+    if int(k) < 1:
+        raise ValueError("k: need k >= 1, got %r" % (k,))
+    k = min(int(k), int(n))
+    if k > MAX_K:
+        raise ValueError("k: at most %d neighbours, got %d" % (MAX_K, k))
+    return k
+
+
+def build_patches(clouds, sample_idx, k, dense=None, normals=None, rotation=None, scale=None, jitter=None, centres=None,
+                  validate=True):
+    """One batch from the device data set ``clouds`` f32 [S,n,3] (``dense`` [S,g,3], ``normals`` [S,n,3] optional).
+
+    ``sample_idx`` int64 [b]: the samples (repeats allowed); ``rotation`` [b,3,3], ``scale`` [b], ``jitter`` [b,n,3]: the
+    augmentation of every entry (each optional); ``centres`` int32 [b,pc]: the patch centres, None = every point in order;
+    ``k`` is clamped to n as the reference's ``min(k, len)`` does.  -> dict of device tensors: ``patches`` [b,pc,k,3], ``idx``
+    int32 [b,pc,k], ``cloud`` [b,n,3], with dense ``dense`` [b,g,3] and ``len`` [b,n], with normals ``normals`` [b,n,3] and
+    ``patch_normals`` [b,pc,3].  Index VALUES are checked here (one synchronisation; ``validate=False`` skips it — the kernels
+    then leave the rows of a bad index unwritten, NaN): ValueError.  CPU tensors: RuntimeError; bad shapes: ValueError."""
+    def dev_tensor(t, name, dtype, shape):
+        if t is None:
+            return None
+        if not torch.is_tensor(t):
+            raise ValueError("%s: expected a device tensor" % name)
+        if not t.is_cuda:
+            raise RuntimeError("%s: a CPU tensor (there is no CPU path)" % name)
+        if t.dim() != len(shape) or any(w is not None and s != w for s, w in zip(t.shape, shape)):
+            raise ValueError("%s: expected shape %s, got %s" % (name, list(shape), list(t.shape)))
+        if t.device != clouds.device:
+            raise ValueError("%s: on %s, the clouds are on %s" % (name, t.device, clouds.device))
+        if dtype.is_floating_point != t.dtype.is_floating_point:
+            raise ValueError("%s: expected %s, got %s" % (name, dtype, t.dtype))
+        return t.to(dtype).contiguous()
+
+    if not torch.is_tensor(clouds):
+        raise ValueError("clouds: expected a device tensor")
+    if not clouds.is_cuda:
+        raise RuntimeError("clouds: a CPU tensor (there is no CPU path)")
+    clouds = dev_tensor(clouds, "clouds", torch.float32, (None, None, 3))
+    S, n = clouds.shape[0], clouds.shape[1]
+    if S < 1 or not 1 <= n <= MAX_N:
+        raise ValueError("clouds: need at least one sample and 1 <= n <= %d points, got %s" % (MAX_N, list(clouds.shape)))
+    dense = dev_tensor(dense, "dense", torch.float32, (S, None, 3))
+    g = 0 if dense is None else dense.shape[1]
+    if dense is not None and not 1 <= g <= MAX_G:
+        raise ValueError("dense: need 1 <= g <= %d points, got %d" % (MAX_G, g))
+    normals = dev_tensor(normals, "normals", torch.float32, (S, n, 3))
+    sample_idx = dev_tensor(sample_idx, "sample_idx", torch.int64, (None,))
+    b = sample_idx.shape[0]
+    rotation = dev_tensor(rotation, "rotation", torch.float32, (b, 3, 3))
+    scale = dev_tensor(scale, "scale", torch.float32, (b,))
+    jitter = dev_tensor(jitter, "jitter", torch.float32, (b, n, 3))
+    centres = dev_tensor(centres, "centres", torch.int32, (b, None))
+    pc = n if centres is None else centres.shape[1]
+    if pc < 1:
+        raise ValueError("centres: need at least one centre per entry")
+    k = clamp_k(k, n)
+    if validate and b:
+        bad = ((sample_idx < 0) | (sample_idx >= S)).sum()
+        if centres is not None:
+            bad = torch.stack([bad, ((centres < 0) | (centres >= n)).sum()])
+        bad = bad.reshape(-1).tolist()
+        if bad[0]:
+            raise ValueError("sample_idx: %d indices outside [0, %d)" % (bad[0], S))
+        if len(bad) > 1 and bad[1]:
+            raise ValueError("centres: %d indices outside [0, %d)" % (bad[1], n))
+
+    dev, nan = clouds.device, float("nan")
+    out = {"patches": torch.full((b, pc, k, 3), nan, dtype=torch.float32, device=dev),
+           "idx": torch.full((b, pc, k), -1, dtype=torch.int32, device=dev),
+           "cloud": torch.full((b, n, 3), nan, dtype=torch.float32, device=dev)}
+    if dense is not None:
+        out["dense"] = torch.full((b, g, 3), nan, dtype=torch.float32, device=dev)
+        out["len"] = torch.full((b, n), nan, dtype=torch.float32, device=dev)
+    if normals is not None:
+        out["normals"] = torch.full((b, n, 3), nan, dtype=torch.float32, device=dev)
+        out["patch_normals"] = torch.full((b, pc, 3), nan, dtype=torch.float32, device=dev)
+    if b == 0:
+        return out
+    lib = _lib.load()
+    nbytes = int(lib.sapcu_train_patches_workspace_bytes(b))
+    if nbytes < 0:
+        raise ValueError("sample_idx: a batch of %d entries is outside the range of the call" % b)
+    ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(lib.sapcu_train_patches_f32(
+            p(clouds), S, n, p(dense), g, p(normals), p(sample_idx), b, p(rotation), p(scale), p(jitter), p(centres), pc, k,
+            p(out["patches"]), p(out["idx"]), p(out["cloud"]), p(out.get("dense")), p(out.get("len")), p(out.get("normals")),
+            p(out.get("patch_normals")), p(ws), nbytes, _lib.current_stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ loaders
+def split_range(total, split):
+    """The reference's split: the first int(0.9 * total) samples train, the rest val (anything else: all)."""
+    cut = int(total * 0.9)
+    if split == "train":
+        return 0, cut
+    if split == "val":
+        return cut, total
+    return 0, total
+
+
+def _array(x, key, name):
+    """A data-set array from a numpy array, a tensor, or a path (.npy; .npz / h5 under the reference's key)."""
+    if isinstance(x, (str, os.PathLike)):
+        path = os.fspath(x)
+        ext = os.path.splitext(path)[1].lower()
+        if ext == ".npy":
+            x = np.load(path)
+        elif ext == ".npz":
+            with np.load(path) as z:
+                if key not in z:
+                    raise ValueError("%s: %s holds no array %r" % (name, path, key))
+                x = z[key]
+        elif ext in (".h5", ".hdf5"):
+            try:
+                import h5py
+            except ImportError as e:
+                raise RuntimeError("%s: reading %s needs h5py, which is not installed (convert to .npz)" % (name, path)) from e
+            with h5py.File(path, "r") as f:
+                x = f[key][:]
+        else:
+            raise ValueError("%s: %s is neither .npy, .npz nor .h5" % (name, path))
+    if torch.is_tensor(x):
+        if not x.dtype.is_floating_point:
+            raise ValueError("%s: expected a floating dtype" % name)
+        t = x
+    else:
+        x = np.asarray(x)
+        if x.dtype.kind != "f":
+            raise ValueError("%s: expected a floating dtype" % name)
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError("%s: expected [S, n, 3], got %s" % (name, list(t.shape)))
+    return t
+
+
+class _DeviceLoader(object):
+    """What the two loaders share: the split, the resident arrays, the batch order and the augmentation draws."""
+
+    JITTER_SIGMA = 0.002
+    SCALE_RANGE = (0.8, 1.2)
+
+    def __init__(self, first, second, names, split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last):
+        if split not in ("train", "val", "all"):
+            raise ValueError("split must be 'train', 'val' or 'all'")
+        if int(batch_size) < 1 or int(k_neighbors) < 1:
+            raise ValueError("batch_size and k_neighbors must be >= 1")
+        a, b = first, second
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("%s and %s: %d and %d samples" % (names[0], names[1], a.shape[0], b.shape[0]))
+        if not 1 <= a.shape[1] <= MAX_N:
+            raise ValueError("%s: need 1 <= n <= %d points per sample" % (names[0], MAX_N))
+        lo, hi = split_range(a.shape[0], split)
+        if hi <= lo:
+            raise ValueError("the %s split of %d samples is empty" % (split, a.shape[0]))
+        clamp_k(k_neighbors, a.shape[1])
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("device %s: there is no CPU path" % dev)
+        self.split, self.device = split, dev
+        self._a = a[lo:hi].to(device=dev, dtype=torch.float32).contiguous()       # uploaded once, kept in HBM
+        self._b = b[lo:hi].to(device=dev, dtype=torch.float32).contiguous()
+        self.k_neighbors, self.batch_size, self.shuffle = int(k_neighbors), int(batch_size), bool(shuffle)
+        self.augment = (split == "train") if augment is None else bool(augment)
+        self.seed, self.epoch, self.drop_last = int(seed), 0, bool(drop_last)
+        self.last_draws = None                                                    # the draws of the batch yielded last (tests, logs)
+
+    @property
+    def samples(self):
+        return self._a.shape[0]
+
+    def __len__(self):
+        return self.samples // self.batch_size if self.drop_last else -(-self.samples // self.batch_size)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+        return self
+
+    def _generator(self, batch):
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(((self.seed * 1000003 + self.epoch) * 1000003 + batch + 1) & (2 ** 63 - 1))
+        return gen
+
+    def _draws(self, gen, b):
+        """(rotation [b,3,3], scale [b], jitter [b,n,3], theta [b]) or four None."""
+        if not self.augment:
+            return None, None, None, None
+        dev, n = self.device, self._a.shape[1]
+        theta = torch.rand((b,), generator=gen, device=dev, dtype=torch.float64) * (2 * math.pi)
+        lo, hi = self.SCALE_RANGE
+        scale = (lo + (hi - lo) * torch.rand((b,), generator=gen, device=dev, dtype=torch.float64)).float()
+        jitter = torch.randn((b, n, 3), generator=gen, device=dev, dtype=torch.float32) * self.JITTER_SIGMA
+        c, s = torch.cos(theta).float(), torch.sin(theta).float()                 # the reference builds its f32 matrix from f64 cos / sin
+        rot = torch.zeros((b, 3, 3), dtype=torch.float32, device=dev)
+        rot[:, 0, 0], rot[:, 0, 1], rot[:, 1, 0], rot[:, 1, 1], rot[:, 2, 2] = c, -s, s, c, 1.0
+        return rot, scale, jitter, theta
+
+    def __iter__(self):
+        order_gen = self._generator(-1)
+        S = self.samples
+        order = torch.randperm(S, generator=order_gen, device=self.device) if self.shuffle else torch.arange(S, device=self.device)
+        for bi in range(len(self)):
+            idx = order[bi * self.batch_size:(bi + 1) * self.batch_size].to(torch.int64)
+            yield self._batch(idx, self._generator(bi))
+
+
+class PU1KPatches(_DeviceLoader):
+    """The stacked batches of the reference's ``PU1KDataset`` (fd/datacore.py; the data set fd/config.py selects): ``input``
+    [B,n,M,3] (M = min(k_neighbors, n)), ``len`` [B,n], ``cloud`` [B,n,3], ``points`` [B,g,3], f32 on the device, plus ``index``
+    (the samples' positions in the split).  ``inputs`` [S,256,3] / ``dense`` [S,1024,3]: numpy arrays, tensors, or .npy / .npz (/ .h5
+    where h5py imports) paths with the reference's keys ``poisson_256`` / ``poisson_1024``."""
+
+    def __init__(self, inputs, dense, split="train", k_neighbors=32, batch_size=4, shuffle=True, augment=None, seed=0, device=None,
+                 drop_last=False):
+        a, b = _array(inputs, "poisson_256", "inputs"), _array(dense, "poisson_1024", "dense")
+        if not 1 <= b.shape[1] <= MAX_G:
+            raise ValueError("dense: need 1 <= g <= %d points per sample" % MAX_G)
+        super().__init__(a, b, ("inputs", "dense"), split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last)
+
+    def _batch(self, idx, gen):
+        rot, scale, jitter, theta = self._draws(gen, idx.shape[0])
+        self.last_draws = {"theta": theta, "rotation": rot, "scale": scale, "jitter": jitter}
+        o = build_patches(self._a, idx, self.k_neighbors, dense=self._b, rotation=rot, scale=scale, jitter=jitter, validate=False)
+        return {"input": o["patches"], "len": o["len"], "cloud": o["cloud"], "points": o["dense"], "index": idx}
+
+
+class MeshPatches(_DeviceLoader):
+    """The stacked batches of the reference's ``PU1KMeshDataset`` (fn/datacore.py) from pre-sampled ``points`` [S,n,3] and their
+    face ``normals`` [S,n,3] (parsing .off files and the area-weighted sampling stay on the host): ``input`` [B,P,k,3], ``normal``
+    [B,P,3], ``cloud`` [B,n,3], ``all_normals`` [B,n,3], plus ``centres`` [B,P] and ``index``.  P = num_patches centres drawn per
+    sample without replacement, or every point in order when n <= num_patches."""
+
+    def __init__(self, points, normals, split="train", num_patches=64, k_neighbors=12, batch_size=4, shuffle=True, augment=None, seed=0,
+                 device=None, drop_last=False):
+        a, b = _array(points, "points", "points"), _array(normals, "normals", "normals")
+        if a.shape != b.shape:
+            raise ValueError("points and normals: shapes %s and %s" % (list(a.shape), list(b.shape)))
+        if int(num_patches) < 1:
+            raise ValueError("num_patches must be >= 1")
+        super().__init__(a, b, ("points", "normals"), split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last)
+        self.num_patches = int(num_patches)
+
+    def _batch(self, idx, gen):
+        b, n = idx.shape[0], self._a.shape[1]
+        rot, scale, jitter, theta = self._draws(gen, b)
+        centres = None
+        if n > self.num_patches:                                                  # a random subset per sample: the first P of a random order
+            keys = torch.rand((b, n), generator=gen, device=self.device)
+            centres = torch.argsort(keys, dim=1)[:, :self.num_patches].to(torch.int32).contiguous()
+        self.last_draws = {"theta": theta, "rotation": rot, "scale": scale, "jitter": jitter, "centres": centres}
+        o = build_patches(self._a, idx, self.k_neighbors, normals=self._b, rotation=rot, scale=scale, jitter=jitter, centres=centres,
+                          validate=False)
+        if centres is None:
+            centres = torch.arange(n, dtype=torch.int32, device=self.device).expand(b, n)
+        return {"input": o["patches"], "normal": o["patch_normals"], "cloud": o["cloud"], "all_normals": o["normals"],
+                "centres": centres, "index": idx}
