@@ -6,6 +6,8 @@ Public surface = the reference's own interface for this path:
   Generator3D6, SNNPointCloudGenerator                        (``generation``)
   normalize_pointcloud, farthest_point_sample, process_file   (``generate``)
   cloud_metrics, dataset_metrics, evaluate_file               (``metrics``: Chamfer, Hausdorff, F-score on the device)
+  point_to_mesh, mesh_metrics, mesh_dataset_metrics,          (``mesh``: P2F, the point-to-surface distance to a triangle mesh,
+  read_off, evaluate_mesh_file                                 on the device)
   build_patches, PU1KPatches, MeshPatches                     (``data``: fd / fn training batches from raw cloud pairs on the device)
 Importing the package never touches the GPU; the HIP library is loaded on first use and its
 absence raises ``SapcuLibraryError`` (no CPU fallback exists).
@@ -15,6 +17,7 @@ from .modules import ImprovedSNNNormalEstimation, EnhancedSNNDistanceEstimation,
 from .generation import Generator3D6, SNNPointCloudGenerator  # noqa: F401
 from .pipeline import normalize_pointcloud, farthest_point_sample, process_cloud, process_file, evaluate_file  # noqa: F401
 from .metrics import cloud_metrics, dataset_metrics  # noqa: F401
+from .mesh import point_to_mesh, mesh_metrics, mesh_dataset_metrics, read_off, evaluate_mesh_file  # noqa: F401
 from .data import build_patches, PU1KPatches, MeshPatches  # noqa: F401
 
 __all__ = ["ImprovedSNNNormalEstimation", "EnhancedSNNDistanceEstimation", "TrainableSNNDistanceEstimation", "Generator3D6",

@@ -145,9 +145,20 @@ _DATA_SIGNATURES = {
 }
 DATA_EXPORTS = tuple(_DATA_SIGNATURES)
 
+# include/sapcu_mesh.h: the distance from every query to a triangle mesh, nearest face and closest point (an eighth table)
+_MESH_SIGNATURES = {
+    "sapcu_point_mesh_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "sapcu_point_mesh_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+}
+MESH_EXPORTS = tuple(_MESH_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    # sapcu_point_mesh_f64 with the oversize cap (in cell edges) and the cell population given, or forced to the brute-force route: profiles/mesh_dist.py, tests/test_gpu_mesh.py
+    "sapcu_internal_point_mesh_tuned": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
 }
 _lib = None
 
@@ -168,7 +179,7 @@ def load(path=None):
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
             list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
-            list(_DATA_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+            list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

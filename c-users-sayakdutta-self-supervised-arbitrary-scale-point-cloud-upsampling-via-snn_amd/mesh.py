@@ -1,0 +1,203 @@
+"""P2F, the point-to-surface distance of a predicted cloud to the ground-truth triangle mesh, on the device.
+
+The third figure an upsampler is judged on, beside Chamfer and Hausdorff distance (``metrics``).  The reference computes it on the
+host with a CGAL program, ``external/Meta-PU_evaluation/evaluation_code/evaluation.cpp`` (``evaluation mesh.off pred.xyz``), which
+writes one distance per point and prints their mean, sample standard deviation, minimum and maximum.  Here the distances are one
+call of ``sapcu_point_mesh_f64`` (csrc/mesh_dist.hip, include/sapcu_mesh.h: the definition, the skipped faces, the caveat about
+slivers), and every float equals numpy's (``==``) on the same distance vector, through the fixed summation order of ``metrics``.
+
+Distances stay f64.  The tool stores each distance as ``float`` and prints six digits; that rounding is NOT reproduced, so a value
+agrees with the tool's to about 5e-6 relative, not bit for bit.  The tool's uniformity figures (geodesic disks on the mesh) are
+not computed here.
+
+No CPU path: the HIP library and a device are required (``read_off`` alone runs on the host).
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import metrics
+
+
+def point_to_mesh(points, vertices, faces, cell_size=0.0, info=None):
+    """Distance from every point f64 [nq,3] to the mesh (``vertices`` f64 [nv,3], ``faces`` integer [nf,3]):
+    (dist f64 [nq], face int64 [nq], closest f64 [nq,3]) on the device — the distance, the nearest face (the lowest index among faces
+    at a bit-equal distance) and the closest point on it.  Inputs are numpy arrays or device tensors.  A face index outside [0, nv)
+    raises ``ValueError`` here (the C entry point would skip that face); zero-area faces are skipped by the kernel and counted.
+    A point that no face gives a distance for (a NaN point, every face skipped) gets NaN, -1, NaN.  ``cell_size`` 0 = automatic
+    (any value gives the same result, bit for bit).  ``info``, a list, receives [route (0 brute force, 1 grid), gx, gy, gz, faces
+    on the oversize list, faces skipped].  Synchronises the current stream once."""
+    points, vertices, faces = _on_device(points, vertices, faces)
+    lib = _lib.load()
+    nq, nv, nf = points.shape[0], vertices.shape[0], faces.shape[0]
+    dev = vertices.device
+    dist = torch.full((nq,), float("nan"), dtype=torch.float64, device=dev)
+    face = torch.full((nq,), -1, dtype=torch.int64, device=dev)
+    closest = torch.full((nq, 3), float("nan"), dtype=torch.float64, device=dev)
+    out = (ctypes.c_int64 * 6)()
+    if nq:
+        nbytes = int(lib.sapcu_point_mesh_workspace_bytes(nv, nf, nq))
+        if nbytes < 0:
+            raise ValueError("point_to_mesh: %d vertices, %d faces and %d points are outside the search's range" % (nv, nf, nq))
+        ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.sapcu_point_mesh_f64(_lib.ptr(vertices), nv, _lib.ptr(faces), nf, _lib.ptr(points), nq, float(cell_size),
+                                                _lib.ptr(dist), _lib.ptr(face), _lib.ptr(closest), _lib.ptr(ws), nbytes, out,
+                                                _lib.current_stream()))
+    if info is not None:
+        info[:] = list(out)
+    return dist, face, closest
+
+
+def mesh_metrics(pred, vertices, faces):
+    """The P2F figures of one predicted cloud against its mesh, a dict: ``p2f_mean``, ``p2f_std`` (the SAMPLE standard deviation,
+    n - 1, as the reference's tool prints; NaN for a single point), ``p2f_min``, ``p2f_max``, ``n_pre``, ``n_faces``, ``n_skipped``
+    (zero-area faces, which take no part).  Floats are ``np.float64`` and equal numpy's on the same distance vector d:
+    ``np.mean(d)``, ``np.sqrt(np.sum((d - mean) ** 2) / (n - 1))``, ``d.min()``, ``d.max()``.  Distances stay f64: the tool's
+    rounding of each distance to ``float`` is not reproduced.  Non-finite input and a mesh whose every face is skipped raise
+    ``ValueError``."""
+    d, nf, ns = _distances(pred, vertices, faces)
+    return _figures(d, nf, ns)
+
+
+def mesh_dataset_metrics(triples):
+    """The pooled figures over ``triples``, an iterable of (pred, vertices, faces): the distance vectors of all clouds concatenated
+    in the order given, then the statistics of ``mesh_metrics`` (``n_pre`` / ``n_faces`` / ``n_skipped``: the pooled counts)."""
+    parts = [_distances(pred, vertices, faces) for pred, vertices, faces in triples]
+    if not parts:
+        raise ValueError("mesh_dataset_metrics: no (pred, vertices, faces) triple")
+    return _figures(torch.cat([d for d, _, _ in parts]), sum(nf for _, nf, _ in parts), sum(ns for _, _, ns in parts))
+
+
+def read_off(path):
+    """A triangle mesh from an ``.off`` text file, on the host: (vertices f64 [nv,3], faces int64 [nf,3]).  Accepted: ``OFF`` with
+    the counts on the same or on the next line, ``#`` comments, blank lines, trailing per-face colour fields.  ``ValueError`` on a
+    face that is not a triangle, on a truncated file and on counts that do not match the file's content."""
+    with open(path) as f:
+        lines = [ln.split("#", 1)[0].split() for ln in f]
+    lines = [t for t in lines if t]
+    if not lines or not lines[0][0].startswith("OFF"):
+        raise ValueError("%s: not an OFF file" % path)
+    head = lines[0][1:] if lines[0][0] == "OFF" else [lines[0][0][3:]] + lines[0][1:]
+    pos = 1
+    if not head:
+        if len(lines) < 2:
+            raise ValueError("%s: truncated before the counts" % path)
+        head, pos = lines[1], 2
+    try:
+        nv, nf = int(head[0]), int(head[1])
+    except (ValueError, IndexError):
+        raise ValueError("%s: bad counts line %r" % (path, " ".join(head))) from None
+    if nv < 0 or nf < 0:
+        raise ValueError("%s: negative counts" % path)
+    if len(lines) < pos + nv + nf:
+        raise ValueError("%s: truncated: %d vertices and %d faces announced, %d lines follow" % (path, nv, nf, len(lines) - pos))
+    if len(lines) > pos + nv + nf:
+        raise ValueError("%s: %d lines beyond the %d vertices and %d faces announced" % (path, len(lines) - pos - nv - nf, nv, nf))
+    vertices = np.zeros((nv, 3), dtype=np.float64)
+    faces = np.zeros((nf, 3), dtype=np.int64)
+    try:
+        for i in range(nv):
+            t = lines[pos + i]
+            if len(t) < 3:
+                raise ValueError("vertex %d has %d coordinates" % (i, len(t)))
+            vertices[i] = [float(t[0]), float(t[1]), float(t[2])]
+        for i in range(nf):
+            t = lines[pos + nv + i]
+            if int(t[0]) != 3:
+                raise ValueError("face %d has %s vertices, not 3" % (i, t[0]))
+            if len(t) < 4:
+                raise ValueError("face %d is truncated" % i)
+            faces[i] = [int(t[1]), int(t[2]), int(t[3])]
+    except ValueError as e:
+        raise ValueError("%s: %s" % (path, e)) from None
+    return vertices, faces
+
+
+def evaluate_mesh_file(pred_path, mesh_path, device="cuda"):
+    """``mesh_metrics`` of a text cloud, loaded the way ``pipeline.evaluate_file`` loads its clouds, against an ``.off`` mesh: what
+    the reference's ``evaluation mesh.off pred.xyz`` prints as Mean / std / min / max (in f64, see the module docstring)."""
+    pred = np.loadtxt(pred_path, ndmin=2)[:, :3]
+    vertices, faces = read_off(mesh_path)
+    dev = torch.device(device)
+    return mesh_metrics(torch.from_numpy(np.ascontiguousarray(pred)).to(dev), torch.from_numpy(vertices).to(dev),
+                        torch.from_numpy(faces).to(dev))
+
+
+# ------------------------------------------------------------------------------------------------------------ internals
+def _checked_faces(faces):
+    if torch.is_tensor(faces):
+        shape, on_host = tuple(faces.shape), not faces.is_cuda
+        integer = not (faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool)
+    else:
+        faces = np.asarray(faces)
+        shape, on_host, integer = faces.shape, False, faces.dtype.kind in "iu"
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError("faces: expected triangles [nf, 3], got shape %s" % (tuple(shape),))
+    if not integer:
+        raise ValueError("faces: expected an integer dtype")
+    if on_host:
+        raise RuntimeError("faces: a CPU tensor (there is no CPU path; pass a device tensor or a numpy array)")
+    if shape[0] < 1:
+        raise ValueError("faces: an empty mesh")
+    return faces
+
+
+def _on_device(points, vertices, faces):
+    """points and vertices as contiguous f64 [n,3], faces as contiguous int32 [nf,3] with every index in [0, nv), on one device."""
+    points, vertices = metrics._checked(points, "points"), metrics._checked(vertices, "vertices")
+    faces = _checked_faces(faces)
+    nv = vertices.shape[0]
+    if nv < 1:
+        raise ValueError("vertices: an empty mesh")
+    dev = next((t.device for t in (points, vertices, faces) if torch.is_tensor(t)), None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    out = []
+    for x in (points, vertices):
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        out.append(x.to(device=dev, dtype=torch.float64).contiguous())
+    if not torch.is_tensor(faces):
+        if faces.dtype.kind == "u":
+            if int(faces.max()) >= nv:
+                raise ValueError("faces: an index outside [0, %d)" % nv)
+        faces = torch.from_numpy(np.ascontiguousarray(faces).astype(np.int64))
+    faces = faces.to(device=dev)
+    lo, hi = int(faces.min()), int(faces.max())
+    if lo < 0 or hi >= nv:
+        raise ValueError("faces: an index outside [0, %d) (smallest %d, largest %d)" % (nv, lo, hi))
+    out.append(faces.to(torch.int32).contiguous())
+    return out
+
+
+def _distances(pred, vertices, faces):
+    """(dist f64 [n_pre] on the device, faces, skipped faces); the input checks of mesh_metrics."""
+    pred, vertices = metrics._checked(pred, "pred"), metrics._checked(vertices, "vertices")
+    if pred.shape[0] < 1:
+        raise ValueError("pred: an empty cloud")
+    for x, name in ((pred, "pred"), (vertices, "vertices")):
+        if not torch.is_tensor(x) and not np.isfinite(x).all():
+            raise ValueError("%s contains NaN or infinity" % name)
+    pred, vertices, faces = _on_device(pred, vertices, faces)
+    for x, name in ((pred, "pred"), (vertices, "vertices")):
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("%s contains NaN or infinity" % name)
+    info = []
+    d = point_to_mesh(pred, vertices, faces, info=info)[0]
+    nf = int(faces.shape[0])
+    if info[5] >= nf:
+        raise ValueError("mesh: every one of the %d faces has zero area" % nf)
+    return d, nf, int(info[5])
+
+
+def _figures(d, n_faces, n_skipped, bufsize=None):
+    n = d.numel()
+    mean = np.float64(metrics._np_sum(d, bufsize)) / n
+    x = d - float(mean)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        std = np.sqrt(np.float64(metrics._np_sum(x * x, bufsize)) / np.float64(n - 1))
+    return {"p2f_mean": mean, "p2f_std": std, "p2f_min": np.float64(d.min().item()), "p2f_max": np.float64(d.max().item()),
+            "n_pre": int(n), "n_faces": int(n_faces), "n_skipped": int(n_skipped)}
