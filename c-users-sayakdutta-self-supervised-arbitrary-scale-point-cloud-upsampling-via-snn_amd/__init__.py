@@ -8,7 +8,9 @@ Public surface = the reference's own interface for this path:
   cloud_metrics, dataset_metrics, evaluate_file               (``metrics``: Chamfer, Hausdorff, F-score on the device)
   point_to_mesh, mesh_metrics, mesh_dataset_metrics,          (``mesh``: P2F, the point-to-surface distance to a triangle mesh,
   read_off, evaluate_mesh_file                                 on the device)
-  build_patches, PU1KPatches, MeshPatches                     (``data``: fd / fn training batches from raw cloud pairs on the device)
+  build_patches, PU1KPatches, MeshPatches,                    (``data``: fd / fn training batches from raw cloud pairs, or from
+  MeshSurfacePatches                                           triangle meshes sampled afresh per batch, on the device)
+  build_surface_tables, sample_surface                        (``surface``: area-weighted sampling of triangle meshes on the device)
 Importing the package never touches the GPU; the HIP library is loaded on first use and its
 absence raises ``SapcuLibraryError`` (no CPU fallback exists).
 """
@@ -18,7 +20,8 @@ from .generation import Generator3D6, SNNPointCloudGenerator  # noqa: F401
 from .pipeline import normalize_pointcloud, farthest_point_sample, process_cloud, process_file, evaluate_file  # noqa: F401
 from .metrics import cloud_metrics, dataset_metrics  # noqa: F401
 from .mesh import point_to_mesh, mesh_metrics, mesh_dataset_metrics, read_off, evaluate_mesh_file  # noqa: F401
-from .data import build_patches, PU1KPatches, MeshPatches  # noqa: F401
+from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches  # noqa: F401
+from .surface import build_surface_tables, sample_surface  # noqa: F401
 
 __all__ = ["ImprovedSNNNormalEstimation", "EnhancedSNNDistanceEstimation", "TrainableSNNDistanceEstimation", "Generator3D6",
            "SNNPointCloudGenerator", "SapcuError", "SapcuLibraryError"]

@@ -153,6 +153,16 @@ _MESH_SIGNATURES = {
 }
 MESH_EXPORTS = tuple(_MESH_SIGNATURES)
 
+# include/sapcu_surface.h: area-weighted sampling of triangle meshes, fn's training clouds from .off files (a ninth table)
+_SURFACE_SIGNATURES = {
+    "sapcu_surface_tables_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "sapcu_surface_tables_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 4 +
+                                 [c_void_p, c_int64, c_void_p]),
+    "sapcu_surface_sample_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_int64, c_int] + [c_void_p] * 3 + [c_void_p] * 3 + [c_void_p]),
+}
+SURFACE_EXPORTS = tuple(_SURFACE_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -179,7 +189,8 @@ def load(path=None):
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
             list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
-            list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_INTERNAL_SIGNATURES.items()):
+            list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_SURFACE_SIGNATURES.items()) + \
+            list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

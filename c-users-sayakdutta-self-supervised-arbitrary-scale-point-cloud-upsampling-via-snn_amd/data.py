@@ -7,7 +7,7 @@ mesh points with their face normals, 64 random centres).  Here the data set is u
 ``sapcu_train_patches_f32`` (csrc/train_patches.hip, include/sapcu_data.h): three launches, no host read-back.  Given the same
 augmentation draws every output equals the reference's bit for bit, up to its BLAS rotation product.
 
-``PU1KPatches`` / ``MeshPatches`` are iterables of stacked batch dicts with the reference's keys; they plug into
+``PU1KPatches`` / ``MeshPatches`` / ``MeshSurfacePatches`` are iterables of stacked batch dicts with the reference's keys; they plug into
 ``train_step.run_epoch(trainer, loader)`` for ``fd_trainer`` / ``fn_trainer``.  The draws (angle, scale, jitter, centres, order) come
 from a device ``torch.Generator`` seeded by (seed, epoch, batch): deterministic, and not the reference's numpy stream.
 
@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mesh as mesh_mod, surface
 
 MAX_N, MAX_G, MAX_K = 4096, 65536, 128
 
@@ -171,33 +171,39 @@ class _DeviceLoader(object):
     SCALE_RANGE = (0.8, 1.2)
 
     def __init__(self, first, second, names, split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last):
+        a, b = first, second
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("%s and %s: %d and %d samples" % (names[0], names[1], a.shape[0], b.shape[0]))
+        lo, hi = self._configure(a.shape[0], a.shape[1], names[0], split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last)
+        self._a = a[lo:hi].to(device=self.device, dtype=torch.float32).contiguous()       # uploaded once, kept in HBM
+        self._b = b[lo:hi].to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _configure(self, total, n, name, split, k_neighbors, batch_size, shuffle, augment, seed, device, drop_last):
+        """The checks and settings every loader shares, for a data set of `total` samples of n points -> the split's range."""
         if split not in ("train", "val", "all"):
             raise ValueError("split must be 'train', 'val' or 'all'")
         if int(batch_size) < 1 or int(k_neighbors) < 1:
             raise ValueError("batch_size and k_neighbors must be >= 1")
-        a, b = first, second
-        if a.shape[0] != b.shape[0]:
-            raise ValueError("%s and %s: %d and %d samples" % (names[0], names[1], a.shape[0], b.shape[0]))
-        if not 1 <= a.shape[1] <= MAX_N:
-            raise ValueError("%s: need 1 <= n <= %d points per sample" % (names[0], MAX_N))
-        lo, hi = split_range(a.shape[0], split)
+        if not 1 <= n <= MAX_N:
+            raise ValueError("%s: need 1 <= n <= %d points per sample" % (name, MAX_N))
+        lo, hi = split_range(total, split)
         if hi <= lo:
-            raise ValueError("the %s split of %d samples is empty" % (split, a.shape[0]))
-        clamp_k(k_neighbors, a.shape[1])
+            raise ValueError("the %s split of %d samples is empty" % (split, total))
+        clamp_k(k_neighbors, n)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("device %s: there is no CPU path" % dev)
         self.split, self.device = split, dev
-        self._a = a[lo:hi].to(device=dev, dtype=torch.float32).contiguous()       # uploaded once, kept in HBM
-        self._b = b[lo:hi].to(device=dev, dtype=torch.float32).contiguous()
+        self._count, self._n = hi - lo, int(n)
         self.k_neighbors, self.batch_size, self.shuffle = int(k_neighbors), int(batch_size), bool(shuffle)
         self.augment = (split == "train") if augment is None else bool(augment)
         self.seed, self.epoch, self.drop_last = int(seed), 0, bool(drop_last)
         self.last_draws = None                                                    # the draws of the batch yielded last (tests, logs)
+        return lo, hi
 
     @property
     def samples(self):
-        return self._a.shape[0]
+        return self._count
 
     def __len__(self):
         return self.samples // self.batch_size if self.drop_last else -(-self.samples // self.batch_size)
@@ -215,7 +221,7 @@ class _DeviceLoader(object):
         """(rotation [b,3,3], scale [b], jitter [b,n,3], theta [b]) or four None."""
         if not self.augment:
             return None, None, None, None
-        dev, n = self.device, self._a.shape[1]
+        dev, n = self.device, self._n
         theta = torch.rand((b,), generator=gen, device=dev, dtype=torch.float64) * (2 * math.pi)
         lo, hi = self.SCALE_RANGE
         scale = (lo + (hi - lo) * torch.rand((b,), generator=gen, device=dev, dtype=torch.float64)).float()
@@ -256,7 +262,7 @@ class PU1KPatches(_DeviceLoader):
 
 class MeshPatches(_DeviceLoader):
     """The stacked batches of the reference's ``PU1KMeshDataset`` (fn/datacore.py) from pre-sampled ``points`` [S,n,3] and their
-    face ``normals`` [S,n,3] (parsing .off files and the area-weighted sampling stay on the host): ``input`` [B,P,k,3], ``normal``
+    face ``normals`` [S,n,3] (one fixed sampling per mesh; ``MeshSurfacePatches`` samples the meshes afresh): ``input`` [B,P,k,3], ``normal``
     [B,P,3], ``cloud`` [B,n,3], ``all_normals`` [B,n,3], plus ``centres`` [B,P] and ``index``.  P = num_patches centres drawn per
     sample without replacement, or every point in order when n <= num_patches."""
 
@@ -271,16 +277,78 @@ class MeshPatches(_DeviceLoader):
         self.num_patches = int(num_patches)
 
     def _batch(self, idx, gen):
-        b, n = idx.shape[0], self._a.shape[1]
+        return self._patches(self._a, self._b, idx, idx, gen, {})
+
+    def _patches(self, points, normals, rows, idx, gen, draws):
+        """The augmentation and centre draws, then the batch of rows `rows` of points / normals [*,n,3]; `draws` joins last_draws."""
+        b, n = idx.shape[0], self._n
         rot, scale, jitter, theta = self._draws(gen, b)
         centres = None
         if n > self.num_patches:                                                  # a random subset per sample: the first P of a random order
             keys = torch.rand((b, n), generator=gen, device=self.device)
             centres = torch.argsort(keys, dim=1)[:, :self.num_patches].to(torch.int32).contiguous()
-        self.last_draws = {"theta": theta, "rotation": rot, "scale": scale, "jitter": jitter, "centres": centres}
-        o = build_patches(self._a, idx, self.k_neighbors, normals=self._b, rotation=rot, scale=scale, jitter=jitter, centres=centres,
+        self.last_draws = dict(draws, theta=theta, rotation=rot, scale=scale, jitter=jitter, centres=centres)
+        o = build_patches(points, rows, self.k_neighbors, normals=normals, rotation=rot, scale=scale, jitter=jitter, centres=centres,
                           validate=False)
         if centres is None:
             centres = torch.arange(n, dtype=torch.int32, device=self.device).expand(b, n)
         return {"input": o["patches"], "normal": o["patch_normals"], "cloud": o["cloud"], "all_normals": o["normals"],
                 "centres": centres, "index": idx}
+
+
+def mesh_files(folder):
+    """The .off files of a mesh folder in the reference's order (fn/datacore.py:37-57): those of the category sub-folders when there
+    are any, else the folder's own, sorted by path."""
+    import glob
+    folder = os.fspath(folder)
+    categories = [d for d in os.listdir(folder) if os.path.isdir(os.path.join(folder, d))]
+    if categories:
+        files = [f for c in categories for f in glob.glob(os.path.join(folder, c, "*.off"))]
+    else:
+        files = glob.glob(os.path.join(folder, "*.off"))
+    if not files:
+        raise ValueError("no .off files found in %s" % folder)
+    return sorted(files)
+
+
+class MeshSurfacePatches(MeshPatches):
+    """The stacked batches of the reference's ``PU1KMeshDataset`` (fn/datacore.py) from the meshes themselves: every batch draws a NEW
+    area-weighted sampling of ``num_points`` surface points with their face normals per mesh (``surface.sample_surface``: one launch),
+    then augments, normalises and patches it as ``MeshPatches`` does — the same dict.  ``meshes``: a list of (vertices [nv,3], faces
+    [nf,3]) or a folder of ``.off`` files laid out as the reference expects (``mesh_files``; polygons are fan-triangulated, vertices
+    taken as f32); the split is the reference's, over the meshes.  The sampling tables are built once, here
+    (``surface.build_surface_tables``: ValueError on an empty mesh, a bad face index, a mesh without area).  Per batch the draws are
+    ``u`` (f64), ``r1``, ``r2`` (f64 rounded to f32, as the reference rounds them), then the augmentation's and the centres', in the
+    reference's call order, all from the (seed, epoch, batch) generator; the val split samples too, without augmenting.
+    ``last_draws`` holds them, with the selected ``faces``."""
+
+    def __init__(self, meshes, num_points=512, num_patches=64, k_neighbors=12, split="train", batch_size=4, shuffle=True, augment=None,
+                 seed=0, device=None, drop_last=False):
+        if int(num_patches) < 1:
+            raise ValueError("num_patches must be >= 1")
+        files = None
+        if isinstance(meshes, (str, os.PathLike)):
+            files = mesh_files(meshes)
+            total = len(files)
+        else:
+            meshes = list(meshes)
+            total = len(meshes)
+        lo, hi = self._configure(total, int(num_points), "num_points", split, k_neighbors, batch_size, shuffle, augment, seed, device,
+                                 drop_last)
+        if files is not None:
+            names = files[lo:hi]
+            pairs = [mesh_mod.read_off(f, triangulate=True) for f in names]
+            pairs = [(v.astype(np.float32), f) for v, f in pairs]
+        else:
+            names, pairs = ["mesh %d" % i for i in range(lo, hi)], meshes[lo:hi]
+        self.num_patches = int(num_patches)
+        self.tables = surface.build_surface_tables(pairs, device=self.device, names=names)
+
+    def _batch(self, idx, gen):
+        b, n, dev = idx.shape[0], self._n, self.device
+        u = torch.rand((b, n), generator=gen, device=dev, dtype=torch.float64)
+        r1 = torch.rand((b, n), generator=gen, device=dev, dtype=torch.float64).float()
+        r2 = torch.rand((b, n), generator=gen, device=dev, dtype=torch.float64).float()
+        points, normals, faces = surface.sample_surface(self.tables, idx, n, u, r1, r2, validate=False)
+        rows = torch.arange(b, dtype=torch.int64, device=dev)
+        return self._patches(points, normals, rows, idx, gen, {"u": u, "r1": r1, "r2": r2, "faces": faces})

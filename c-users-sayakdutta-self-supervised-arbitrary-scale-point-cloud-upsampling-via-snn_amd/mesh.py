@@ -71,10 +71,12 @@ def mesh_dataset_metrics(triples):
     return _figures(torch.cat([d for d, _, _ in parts]), sum(nf for _, nf, _ in parts), sum(ns for _, _, ns in parts))
 
 
-def read_off(path):
+def read_off(path, triangulate=False):
     """A triangle mesh from an ``.off`` text file, on the host: (vertices f64 [nv,3], faces int64 [nf,3]).  Accepted: ``OFF`` with
     the counts on the same or on the next line, ``#`` comments, blank lines, trailing per-face colour fields.  ``ValueError`` on a
-    face that is not a triangle, on a truncated file and on counts that do not match the file's content."""
+    face that is not a triangle, on a truncated file and on counts that do not match the file's content.  With ``triangulate`` a
+    polygon of m vertices becomes the fan (0, j, j+1), j = 1..m-2, and a face of fewer than three vertices is dropped, as the
+    reference's training loader does (fn/datacore.py:111-117); nf is then the number of triangles, not the file's face count."""
     with open(path) as f:
         lines = [ln.split("#", 1)[0].split() for ln in f]
     lines = [t for t in lines if t]
@@ -104,13 +106,23 @@ def read_off(path):
             if len(t) < 3:
                 raise ValueError("vertex %d has %d coordinates" % (i, len(t)))
             vertices[i] = [float(t[0]), float(t[1]), float(t[2])]
+        fans = []
         for i in range(nf):
             t = lines[pos + nv + i]
+            if triangulate:
+                m = int(t[0])
+                if m < 0 or len(t) < 1 + m:
+                    raise ValueError("face %d is truncated" % i)
+                corners = [int(c) for c in t[1:1 + m]]
+                fans += [[corners[0], corners[j], corners[j + 1]] for j in range(1, m - 1)]
+                continue
             if int(t[0]) != 3:
                 raise ValueError("face %d has %s vertices, not 3" % (i, t[0]))
             if len(t) < 4:
                 raise ValueError("face %d is truncated" % i)
             faces[i] = [int(t[1]), int(t[2]), int(t[3])]
+        if triangulate:
+            faces = np.array(fans, dtype=np.int64).reshape(-1, 3)
     except ValueError as e:
         raise ValueError("%s: %s" % (path, e)) from None
     return vertices, faces
