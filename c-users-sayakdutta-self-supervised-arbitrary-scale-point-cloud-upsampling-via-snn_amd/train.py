@@ -232,10 +232,37 @@ class _SoftmaxAgg(torch.autograd.Function):
         return ga, gpe, gv, None, None, None, None
 
 
+GROUP_LDS_LIMIT = 64 * 1024     # bytes of LDS launch_scatter_sum_grouped (csrc/train_ops.hip) may use for a group's inverse table
+
+
+def group_lds_bytes(group_src_rows, group_rows):
+    """LDS the deterministic grouped sum needs for a group of `group_rows` index rows into `group_src_rows` destination rows: its
+    tables, 2 group_rows + group_src_rows + 1 ints."""
+    return (2 * int(group_rows) + int(group_src_rows) + 1) * 4
+
+
+def group_fits_backward(group_src_rows, group_rows):
+    """Whether the deterministic grouped sum takes such a group."""
+    return group_lds_bytes(group_src_rows, group_rows) <= GROUP_LDS_LIMIT
+
+
+def _check_group(what, group, *inputs):
+    """The grouped sum runs in the BACKWARD only: when a gradient will be asked for, a group beyond its limit is refused here, in
+    the forward and before this op launches anything (the layers of a model that come before the op have run by then; no gradient
+    exists yet), not later inside loss.backward() with half the gradients computed."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in inputs):
+        need = group_lds_bytes(*group)
+        if need > GROUP_LDS_LIMIT:
+            raise ValueError("%s: a group of %d rows into %d rows needs %d bytes of LDS in the backward, the limit is %d"
+                             % (what, group[1], group[0], need, GROUP_LDS_LIMIT))
+
+
 def softmax_agg(a, pe, v, idx, m, sqrt_hd, keep=None):
     """fn/snn_coder.py:379-389 on edge rows: a, pe [P*k, d]; v [P, d]; idx [P*k] in-patch neighbour indices (m points per
     patch) -> res [P, d] = sum_j softmax_j(a / sqrt_hd) * keep_j * (v[nbr_j] + pe_j).  keep: None, or [P*k, d] holding 0 or
-    1/(1-p) (the attention dropout of train() mode, fn:383).  Differentiable w.r.t. a, pe and v."""
+    1/(1-p) (the attention dropout of train() mode, fn:383).  Differentiable w.r.t. a, pe and v; ValueError when a gradient is
+    needed and a patch's m x k neighbour table is beyond the backward's grouped sum (group_fits_backward)."""
+    _check_group("softmax_agg", (int(m), int(m) * (a.shape[0] // max(v.shape[0], 1))), a, pe, v)
     return _SoftmaxAgg.apply(a, pe, v, idx, m, sqrt_hd, keep)
 
 
@@ -287,7 +314,10 @@ def gather_rows(src, index, group=None):
     """out[r] = src[index[r]] on [rows, d] tensors (index_points, fn/snn_coder.py:19-29); backward = scatter-add.
     group = (destination rows per group, index rows per group) when the index is patch-structured — rows r of group g (a
     patch's m*k edge rows) only point into source rows [g*gs, (g+1)*gs) (the patch's m points): the backward is then the
-    deterministic segmented sum (sapcu_scatter_add_rows_grouped) instead of float atomics."""
+    deterministic segmented sum (sapcu_scatter_add_rows_grouped) instead of float atomics; ValueError when src needs a gradient
+    and the group is beyond that sum's limit (group_fits_backward)."""
+    if group is not None:
+        _check_group("gather_rows", group, src)
     return _GatherRows.apply(src, index, group)
 
 

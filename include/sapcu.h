@@ -216,8 +216,9 @@ int sapcu_conv1x1_wgrad_bf16(const float* grad_y, int ldy, const float* x, int l
  *   res[pt, c] = sum_j softmax_j(a[pt, j, c] / sqrt_hd) * (v[nbr(pt, j), c] + pe[pt, j, c])
  * a, pe, grad_a, grad_pe: [pts*kk, d] (edge rows); v, grad_v: [pts, ld] rows; idx [pts*kk] = in-patch neighbour indices,
  * m points per patch (pts % m == 0).  keep: NULL, or [pts*kk, d] holding 0 or 1/(1-p) — the attention dropout of train()
- * mode applied to the softmax weights (fn/snn_coder.py:383); the caller draws it.  The backward zeroes grad_v[., 0:d] and
- * accumulates with float atomics. */
+ * mode applied to the softmax weights (fn/snn_coder.py:383); the caller draws it.  The backward stores every row of
+ * grad_v[., 0:d] as the deterministic grouped sum of sapcu_scatter_add_rows_grouped over the patch's m*kk edge rows (no atomics,
+ * no zeroing pass): SAPCU_ERR_ARG when a patch's tables, (2 m kk + m + 1) ints, pass 64 KiB of LDS. */
 int sapcu_softmax_agg_forward(const float* a, const float* pe, const float* v, int ldv, const int32_t* idx, const float* keep,
                               int64_t pts, int m, int kk, int d, float sqrt_hd, float* res, void* stream);
 int sapcu_softmax_agg_backward(const float* a, const float* pe, const float* v, int ldv, const int32_t* idx, const float* keep,
