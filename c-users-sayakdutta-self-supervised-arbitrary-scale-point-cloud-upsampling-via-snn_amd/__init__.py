@@ -6,6 +6,8 @@ Public surface = the reference's own interface for this path:
   Generator3D6, SNNPointCloudGenerator                        (``generation``)
   normalize_pointcloud, farthest_point_sample, process_file   (``generate``)
   cloud_metrics, dataset_metrics, evaluate_file               (``metrics``: Chamfer, Hausdorff, F-score on the device)
+  softmin, sinkhorn_potentials, sinkhorn_metrics,             (``sinkhorn``: Sinkhorn / EMD transport figures on the device, without
+  dataset_sinkhorn, evaluate_sinkhorn_file                     the n x m cost matrix)
   point_to_mesh, mesh_metrics, mesh_dataset_metrics,          (``mesh``: P2F, the point-to-surface distance to a triangle mesh,
   read_off, evaluate_mesh_file                                 on the device)
   build_patches, PU1KPatches, MeshPatches,                    (``data``: fd / fn training batches from raw cloud pairs, or from
@@ -17,8 +19,9 @@ absence raises ``SapcuLibraryError`` (no CPU fallback exists).
 from ._lib import SapcuError, SapcuLibraryError, LIB_PATH  # noqa: F401
 from .modules import ImprovedSNNNormalEstimation, EnhancedSNNDistanceEstimation, TrainableSNNDistanceEstimation  # noqa: F401
 from .generation import Generator3D6, SNNPointCloudGenerator  # noqa: F401
-from .pipeline import normalize_pointcloud, farthest_point_sample, process_cloud, process_file, evaluate_file  # noqa: F401
+from .pipeline import normalize_pointcloud, farthest_point_sample, process_cloud, process_file, evaluate_file, evaluate_sinkhorn_file  # noqa: F401
 from .metrics import cloud_metrics, dataset_metrics  # noqa: F401
+from .sinkhorn import softmin, sinkhorn_potentials, sinkhorn_metrics, dataset_sinkhorn  # noqa: F401
 from .mesh import point_to_mesh, mesh_metrics, mesh_dataset_metrics, read_off, evaluate_mesh_file  # noqa: F401
 from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches  # noqa: F401
 from .surface import build_surface_tables, sample_surface  # noqa: F401

@@ -163,12 +163,28 @@ _SURFACE_SIGNATURES = {
 }
 SURFACE_EXPORTS = tuple(_SURFACE_SIGNATURES)
 
+# include/sapcu_sinkhorn.h: entropic optimal transport between two clouds without the cost matrix (a tenth table)
+_SINKHORN_SIGNATURES = {
+    "sapcu_sinkhorn_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "sapcu_softmin_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_double, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sapcu_sinkhorn_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(c_double), c_int64, c_double, c_int64, c_void_p,
+                                   c_void_p, c_void_p, c_int64, c_void_p]),
+    "sapcu_plan_stats_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_void_p]),
+}
+SINKHORN_EXPORTS = tuple(_SINKHORN_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     # sapcu_point_mesh_f64 with the oversize cap (in cell edges) and the cell population given, or forced to the brute-force route: profiles/mesh_dist.py, tests/test_gpu_mesh.py
     "sapcu_internal_point_mesh_tuned": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    # csrc/sinkhorn.hip: {tile, shortest planned chunk, chunks, columns per chunk} of rows x columns (host only), and sapcu_softmin_f64
+    # with the number of column chunks forced (chunks without a column): sapcu_amd/sinkhorn.py, tests/test_gpu_sinkhorn.py
+    "sapcu_internal_sinkhorn_split": (c_int, [c_int64, c_int64, POINTER(c_int64)]),
+    "sapcu_internal_softmin_split_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p,
+                                                 c_int64, c_void_p]),
 }
 _lib = None
 
@@ -190,6 +206,7 @@ def load(path=None):
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
             list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
             list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_SURFACE_SIGNATURES.items()) + \
+            list(_SINKHORN_SIGNATURES.items()) + \
             list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)

@@ -85,3 +85,13 @@ def evaluate_file(pred_path, gt_path, device="cuda"):
     pred, gt = np.loadtxt(pred_path, ndmin=2)[:, :3], np.loadtxt(gt_path, ndmin=2)[:, :3]
     dev = torch.device(device)
     return metrics.cloud_metrics(torch.from_numpy(np.ascontiguousarray(pred)).to(dev), torch.from_numpy(np.ascontiguousarray(gt)).to(dev))
+
+
+def evaluate_sinkhorn_file(pred_path, gt_path, device="cuda", **settings):
+    """The transport figures of two text clouds (``sinkhorn.sinkhorn_metrics`` and its settings: p, blur, iters, scaling, debias,
+    downsample_gt), loaded the way ``evaluate_file`` loads them."""
+    from . import sinkhorn
+    pred, gt = np.loadtxt(pred_path, ndmin=2)[:, :3], np.loadtxt(gt_path, ndmin=2)[:, :3]
+    dev = torch.device(device)
+    return sinkhorn.sinkhorn_metrics(torch.from_numpy(np.ascontiguousarray(pred)).to(dev), torch.from_numpy(np.ascontiguousarray(gt)).to(dev),
+                                     **settings)
