@@ -31,22 +31,11 @@ def _dev(a):
 
 def _step_ref(x, raw, state, eif):
     """One neuron step of train() mode restated in torch ops (hard spike forward, soft surrogate backward) for the cases that have
-    no reference run: -> spikes, (membrane, threshold, refractory), u."""
-    md, ta, rd = raw["membrane_decay"].clamp(0.1, 0.99), raw["threshold_adapt"].clamp(0.001, 0.1), raw["refractory_decay"].clamp(0.1, 0.95)
-    tb = raw["threshold_base"]
-    m0, th0, r0 = state if state is not None else (torch.zeros_like(x), tb.expand_as(x), torch.zeros_like(x))
-    mm = m0 * md * (1 - r0) + x * (r0 <= 0).float()
-    if eif:
-        dT, rh = raw["delta_T"].clamp(0.1, 5.0), raw["theta_rh"].clamp(0.1, 2.0)
-        mm = mm + dT * torch.exp(((m0 - rh) / (dT + 1e-6)).clamp(-5.0, 5.0))
-    u = mm - th0
-    uc = u.clamp(-10.0, 10.0)
-    soft = 0.5 * torch.exp(-(uc ** 2) / 2) / math.sqrt(2 * math.pi) + 0.5 * torch.sigmoid(10.0 * uc)
-    sp = soft + ((u > 0).float() - soft).detach()
-    m1 = mm * (1 - sp)
-    r1 = r0 * rd + sp
-    th1 = tb + ((th0 + ta * sp) - tb) * 0.95
-    return sp, (m1.detach(), th1.detach(), r1.detach()), u.detach()
+    no reference run: -> spikes, (membrane, threshold, refractory), u.  The arithmetic lives in oracle/train_path.py, where the
+    whole-model oracle uses it (and tests/test_oracle_golden.py pins it on the reference's runs)."""
+    from oracle import train_path as TP
+    assert eif == ("delta_T" in raw)
+    return TP.neuron_step_train(x, raw, state)
 
 
 # ================================================================================================ ops against reference runs

@@ -435,6 +435,87 @@ def test_fn_trainer_step_matches_reference():
     check_fn_trainer_updates(g, new, {n: p[n] for n in names}, names, 2e-2, 5e-5)
 
 
+@pytest.mark.parametrize("cfg", ["A", "B"])
+def test_fd_training_step_matches_reference(cfg):
+    """Row f-5: one training step of the WHOLE fd model (train() mode, dropout 0) — oracle.train_path.fd_train_forward in f32,
+    forced on the reference's own kNN tables and hard spikes, against what tests/golden/fd_train.npz (A) and fd_train_b.npz (B)
+    store of the reference's run: pooled / integrated taps, prediction, loss, every gradient (check_fn_train_grads, and the row
+    norms of the three large tensors), the grad-is-None and exactly-zero sets, the BatchNorm buffers and num_batches_tracked, and
+    the oracle's own spikes (u > 0) against the reference's.
+
+    Both sides are CPU torch in f32: only the summation order differs.  Measured on two hosts with different CPUs (on each, 1 and 8
+    threads give the same figures to the digits shown; the digits depend on the CPU's torch kernels):
+
+        A: pooled 6.2e-06, integrated 2.6e-06, prediction 6.0e-07, loss 1.3e-07; gradients 0.00176 of the device's bar; buffers 7.8e-08
+        B: pooled 6.7e-06, integrated 2.9e-06, prediction 8.6e-07, loss 6.0e-08; gradients 0.00138 of the device's bar; buffers 1.2e-07
+        A: pooled 5.0e-06, integrated 2.4e-06, prediction 4.8e-07, loss 3.0e-08; gradients 0.00183 of the device's bar; buffers 6.7e-08
+        B: pooled 8.6e-06, integrated 2.9e-06, prediction 3.0e-07, loss 6.0e-08; gradients 0.00694 of the device's bar; buffers 1.2e-07
+
+    The bars are the largest figure of each kind times 4 (thread-count-dependent summation order): 3.4e-5 for the values,
+    4 x 0.00694 = 0.0278 of the device's gradient bar, 4.8e-7 for the buffers (FD_PIN_BARS below) — a sixth of the device's value
+    bar, a thirty-sixth of its gradient bar and a twentieth of its buffer bar (2e-4; 2e-2 / 5e-5; 1e-5).  No spike of either run
+    differs from the reference's."""
+    from oracle import train_path as TP
+    from test_gpu_fd_train import _config
+    kw, g, sd, names = _config(cfg)
+    P, M, Tn, emb = int(g["P"]), int(g["M"]), kw["time_steps_enc"], kw["emb_dims"]
+    p = {n: sd[n].clone().requires_grad_(True) for n in names}
+    p.update({n: v.clone() for n, v in sd.items() if n not in p})
+    spikes = t(np.unpackbits(g["spikes"], axis=-1)[..., :960].astype(np.float32))
+    fc = t(np.unpackbits(g["fc_spikes"], axis=-1)[..., :emb].astype(np.float32))
+    force = {"fc": fc}
+    for s in range(Tn):
+        for b, (lo, hi) in enumerate(((0, 64), (64, 192), (192, 448), (448, 960))):
+            force[(s, b)] = spikes[s, :, lo:hi].contiguous()
+    taps = {}
+    pred = TP.fd_train_forward(p, t(g["input"]), kw["k"], tuple(kw["k_scales"]), Tn, kw["num_heads"], knn=t(g["knn"].astype(np.int64)),
+                               momentum=0.1, taps=taps, force_spikes=force)
+    loss = TP.distance_loss(pred, t(g["gt"]))
+    loss.backward()
+    own = torch.stack([torch.cat([(u > 0).float() for u in taps["preact"][4 * s:4 * s + 4]], dim=1) for s in range(Tn)])
+    assert torch.equal(own, spikes) and torch.equal((taps["fc_preact"][0] > 0).float(), fc)
+    assert torch.equal(torch.stack(taps["knn"]), t(g["knn"].astype(np.int64)))
+    e = {"pooled": float((torch.stack(taps["pooled"]) - t(g["pooled"])).abs().max()),
+         "integrated": float((taps["integrated"][0] - t(g["integrated"])).abs().max()),
+         "prediction": float((pred.detach() - t(g["pred"])).abs().max()), "loss": abs(float(loss.detach()) - float(g["loss"]))}
+    assert {n for n in names if p[n].grad is None} == {str(n) for n in g["grad_none"]}
+    assert {n for n in names if p[n].grad is not None and not bool(p[n].grad.any())} == {str(n) for n in g["grad_zero"]}
+    graded = [n for n in names if p[n].grad is not None]
+    tol, floor_rel = FD_PIN_BARS["grads"]
+    worst = check_fn_train_grads(g, p, graded, tol, floor_rel)
+    # the same comparison as a share of the device's bar 2e-2 max|ref| + 5e-5 peak, the figure the docstring quotes
+    peak = max(float(np.abs(g[("g:" if ("g:" + n) in g else "gs:") + n]).max()) for n in graded)
+    share = 0.0
+    for n in graded:
+        got = p[n].grad.numpy().ravel()
+        ref, got = (g["g:" + n].ravel(), got) if ("g:" + n) in g else (g["gs:" + n], got[g["gi:" + n]])
+        share = max(share, float(np.abs(got - ref).max()) / (2e-2 * float(np.abs(ref).max()) + 5e-5 * peak))
+    big = [n for n in names if ("grn:" + n) in g]
+    assert sorted(big) == ["encoder.conv_blocks.1.0.weight", "encoder.conv_blocks.2.0.weight", "encoder.multi_scale_conv.0.weight"]
+    for n in big:
+        got = np.linalg.norm(p[n].grad.numpy().reshape(p[n].shape[0], -1).astype(np.float64), axis=1)
+        bar = tol * g["grn:" + n].max() + floor_rel * peak * np.sqrt(p[n][0].numel())
+        share = max(share, float(np.abs(got - g["grn:" + n]).max()) / (2e-2 * g["grn:" + n].max() + 5e-5 * peak * np.sqrt(p[n][0].numel())))
+        assert np.abs(got - g["grn:" + n]).max() <= bar, n
+    e_buf = 0.0
+    for n in sd:
+        if n in names:
+            continue
+        if n.endswith("num_batches_tracked"):
+            assert int(p[n]) == int(g["buf:" + n]), n
+        else:
+            e_buf = max(e_buf, float(np.abs(p[n].numpy() - g["buf:" + n]).max()))
+    assert int(p["encoder.scale_fusion.1.num_batches_tracked"]) == Tn and int(p["encoder.conv_blocks.0.1.num_batches_tracked"]) == Tn
+    print("config %s: pooled %.3g, integrated %.3g, prediction %.3g, loss %.3g; gradients %.3g of the device's bar (worst error / scale "
+          "%.3g); buffers %.3g" % (cfg, e["pooled"], e["integrated"], e["prediction"], e["loss"], share, worst, e_buf))
+    assert max(e.values()) <= FD_PIN_BARS["values"], e
+    assert e_buf <= FD_PIN_BARS["buffers"], e_buf
+
+
+# (values: taps, prediction and loss; grads: (tol, floor_rel) of check_fn_train_grads; buffers) — see the docstring above
+FD_PIN_BARS = {"values": 3.4e-5, "grads": (0.0278 * 2e-2, 0.0278 * 5e-5), "buffers": 4.8e-7}
+
+
 def test_reference_against_itself_fixture():
     """tests/golden/ref_vs_ref.npz (make_fixtures.py --only-ref-vs-ref): the REAL reference run with 1 thread and with 8 threads —
     the floor under every free-running fd parity figure quoted in DESIGN.md section 2 and profiles/r03_flip_sources.md.  fd alone is
