@@ -13,6 +13,8 @@ Public surface = the reference's own interface for this path:
   build_patches, PU1KPatches, MeshPatches,                    (``data``: fd / fn training batches from raw cloud pairs, or from
   MeshSurfacePatches                                           triangle meshes sampled afresh per batch, on the device)
   build_surface_tables, sample_surface                        (``surface``: area-weighted sampling of triangle meshes on the device)
+  ray_to_mesh, signed_ray_distance, ray_metrics,              (``ray``: ray casting against triangle meshes on the device, the ground
+  sample_fd_rays, as_fd_npz, is_watertight, FdRayPatches       truth of fd's directed distance, fd's ray samples from meshes)
 Importing the package never touches the GPU; the HIP library is loaded on first use and its
 absence raises ``SapcuLibraryError`` (no CPU fallback exists).
 """
@@ -23,8 +25,9 @@ from .pipeline import normalize_pointcloud, farthest_point_sample, process_cloud
 from .metrics import cloud_metrics, dataset_metrics  # noqa: F401
 from .sinkhorn import softmin, sinkhorn_potentials, sinkhorn_metrics, dataset_sinkhorn  # noqa: F401
 from .mesh import point_to_mesh, mesh_metrics, mesh_dataset_metrics, read_off, evaluate_mesh_file  # noqa: F401
-from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches  # noqa: F401
+from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches, FdRayPatches  # noqa: F401
 from .surface import build_surface_tables, sample_surface  # noqa: F401
+from .ray import ray_to_mesh, signed_ray_distance, ray_metrics, sample_fd_rays, as_fd_npz, is_watertight  # noqa: F401
 
 __all__ = ["ImprovedSNNNormalEstimation", "EnhancedSNNDistanceEstimation", "TrainableSNNDistanceEstimation", "Generator3D6",
            "SNNPointCloudGenerator", "SapcuError", "SapcuLibraryError"]

@@ -174,6 +174,17 @@ _SINKHORN_SIGNATURES = {
 }
 SINKHORN_EXPORTS = tuple(_SINKHORN_SIGNATURES)
 
+# include/sapcu_ray.h: where every ray first meets a triangle mesh, and the fused step of fd's ray sampler (an eleventh table)
+_RAY_SIGNATURES = {
+    "sapcu_ray_mesh_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "sapcu_ray_mesh_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    "sapcu_ray_fd_samples_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "sapcu_ray_fd_samples_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double] +
+                                 [c_void_p] * 4 + [c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+}
+RAY_EXPORTS = tuple(_RAY_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -185,6 +196,11 @@ _INTERNAL_SIGNATURES = {
     "sapcu_internal_sinkhorn_split": (c_int, [c_int64, c_int64, POINTER(c_int64)]),
     "sapcu_internal_softmin_split_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_double, c_int, c_void_p, c_void_p,
                                                  c_int64, c_void_p]),
+    # sapcu_ray_mesh_f64 with the oversize cap and the piece length (in cell edges) and the cell population given, or forced to the
+    # brute-force route: profiles/ray_cast.py, tests/test_gpu_ray.py
+    "sapcu_internal_ray_mesh_tuned": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
+                                              c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64),
+                                              c_void_p]),
 }
 _lib = None
 
@@ -206,7 +222,7 @@ def load(path=None):
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
             list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
             list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_SURFACE_SIGNATURES.items()) + \
-            list(_SINKHORN_SIGNATURES.items()) + \
+            list(_SINKHORN_SIGNATURES.items()) + list(_RAY_SIGNATURES.items()) + \
             list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)

@@ -36,8 +36,9 @@
 //     integer maximum over the bits of non-negative doubles), no scratch.
 // The brute-force kernel runs instead for non-finite or huge (|x| > 1e150) coordinates in vertices or queries, when more than
 // 1 / MESH_OVERSIZE_SHARE_DIV of the faces are oversize, and for nf < MESH_GRID_MIN_FACES with the automatic cell size.
-#include "common.h"
-#include "knn_grid.h"
+// The face record with its skip rule, mesh_dot and the counters live in mesh_common.h, which ray_cast.hip shares; it reaches
+// mesh_prep_kernel and mesh_classify_kernel through launch_mesh_prep / launch_mesh_classify below.
+#include "mesh_common.h"
 #include "../../include/sapcu_mesh.h"
 
 namespace sapcu {
@@ -48,13 +49,6 @@ constexpr int MESH_CELL_POP = 4;
 constexpr int64_t MESH_GRID_MIN_FACES = 1280;
 constexpr double MESH_OVERSIZE_MULT = 2.0;
 constexpr int64_t MESH_OVERSIZE_SHARE_DIV = 4;
-constexpr int MESH_WAVES = 4;
-
-struct MeshCtl {
-    unsigned long long rbits;    // bits of the largest radius among in-grid faces
-    int n_over;                  // faces on the oversize list
-    int n_skip;                  // skipped faces
-};
 
 struct MeshWs {
     GridWs g;                    // the grid over the faces' centroids
@@ -93,47 +87,6 @@ static MeshWs mesh_ws_layout(void* base, int64_t nf, int64_t nq) {
     w.q.bytes = c.bytes();
     w.bytes = w.g.bytes + c.bytes();
     return w;
-}
-
-// ------------------------------------------------------------------------------------------------------ arithmetic
-__device__ __forceinline__ double mesh_dot(double ux, double uy, double uz, double vx, double vy, double vz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(ux, vx), __dmul_rn(uy, vy)), __dmul_rn(uz, vz));
-}
-
-struct __align__(16) MeshFace {
-    double ax, ay, az, bx, by, bz, cx, cy, cz;
-    int idx, pad;                // idx < 0: skipped (or a spare slot of the slab)
-};
-
-struct MeshBest {
-    double d;
-    int f;
-    double qx, qy, qz;
-};
-
-// the face's record; idx = f, or -1 when the face is skipped (an index out of range, dot(n, n) zero or not finite)
-__device__ __forceinline__ MeshFace mesh_load_face(int f, const double* __restrict__ vertices, int64_t nv, const int32_t* __restrict__ faces) {
-    MeshFace m{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -1, 0};
-    const int32_t* t = faces + (int64_t)f * 3;
-    const int64_t i0 = t[0], i1 = t[1], i2 = t[2];
-    if (i0 < 0 || i0 >= nv || i1 < 0 || i1 >= nv || i2 < 0 || i2 >= nv) return m;
-    m.ax = vertices[i0 * 3 + 0];
-    m.ay = vertices[i0 * 3 + 1];
-    m.az = vertices[i0 * 3 + 2];
-    m.bx = vertices[i1 * 3 + 0];
-    m.by = vertices[i1 * 3 + 1];
-    m.bz = vertices[i1 * 3 + 2];
-    m.cx = vertices[i2 * 3 + 0];
-    m.cy = vertices[i2 * 3 + 1];
-    m.cz = vertices[i2 * 3 + 2];
-    const double abx = __dsub_rn(m.bx, m.ax), aby = __dsub_rn(m.by, m.ay), abz = __dsub_rn(m.bz, m.az);
-    const double acx = __dsub_rn(m.cx, m.ax), acy = __dsub_rn(m.cy, m.ay), acz = __dsub_rn(m.cz, m.az);
-    const double nx = __dsub_rn(__dmul_rn(aby, acz), __dmul_rn(abz, acy));
-    const double ny = __dsub_rn(__dmul_rn(abz, acx), __dmul_rn(abx, acz));
-    const double nz = __dsub_rn(__dmul_rn(abx, acy), __dmul_rn(aby, acx));
-    const double nn = mesh_dot(nx, ny, nz, nx, ny, nz);
-    if (nn > 0.0 && nn < __builtin_huge_val()) m.idx = f;
-    return m;
 }
 
 // one face against one query: the definition of include/sapcu_mesh.h
@@ -401,6 +354,21 @@ static int launch_mesh_brute(const double* vertices, int64_t nv, const int32_t* 
     const int64_t grid = (nq + 64 * MESH_WAVES - 1) / (64 * MESH_WAVES);
     hipLaunchKernelGGL(mesh_brute_kernel, dim3((unsigned)grid), dim3(256), 0, st, vertices, nv, faces, (int)nf, queries, nq, dist, face,
                        closest);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+// the two face passes for the other translation units (mesh_common.h)
+int launch_mesh_prep(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, double* centroid, double* radius, MeshCtl* ctl,
+                     hipStream_t st) {
+    hipLaunchKernelGGL(mesh_prep_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, vertices, nv, faces, (int)nf, centroid, radius,
+                       ctl);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
+int launch_mesh_classify(const double* radius, int64_t nf, const GridParams* prm, double mult, int* olist, MeshCtl* ctl, hipStream_t st) {
+    hipLaunchKernelGGL(mesh_classify_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, radius, (int)nf, prm, mult, olist, ctl);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
 }

@@ -10,6 +10,8 @@ augmentation draws every output equals the reference's bit for bit, up to its BL
 ``PU1KPatches`` / ``MeshPatches`` / ``MeshSurfacePatches`` are iterables of stacked batch dicts with the reference's keys; they plug into
 ``train_step.run_epoch(trainer, loader)`` for ``fd_trainer`` / ``fn_trainer``.  The draws (angle, scale, jitter, centres, order) come
 from a device ``torch.Generator`` seeded by (seed, epoch, batch): deterministic, and not the reference's numpy stream.
+``FdRayPatches`` yields fd's ray samples of one mesh per item (the reference's ``scripts/sample_mesh-rd.py`` -> ``fd.npz``), sampled
+and cast afresh on the device (``ray.sample_fd_rays``).
 
 No CPU path: the HIP library and a device are required.
 """
@@ -19,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, mesh as mesh_mod, surface
+from . import _lib, mesh as mesh_mod, ray as ray_mod, surface
 
 MAX_N, MAX_G, MAX_K = 4096, 65536, 128
 
@@ -352,3 +354,73 @@ class MeshSurfacePatches(MeshPatches):
         points, normals, faces = surface.sample_surface(self.tables, idx, n, u, r1, r2, validate=False)
         rows = torch.arange(b, dtype=torch.int64, device=dev)
         return self._patches(points, normals, rows, idx, gen, {"u": u, "r1": r1, "r2": r2, "faces": faces})
+
+
+class FdRayPatches(object):
+    """fd's ray samples straight from meshes: one item per mesh of the split, each a FRESH run of the reference's
+    ``scripts/sample_mesh-rd.py`` on the device (``ray.sample_fd_rays``: ``num_rays`` surface points thrown out along random unit
+    directions by 0.003 .. 0.03 and cast back; the samples whose ray first meets the sampled face at less than 1 rad are kept) — what
+    the reference stores once per mesh as ``fd.npz`` and ``fd/field.py:fdField`` loads.  ``meshes``: a list of (vertices [nv,3],
+    faces [nf,3]) or a folder of ``.off`` files as for ``MeshSurfacePatches`` (vertices taken as f32).  An item is a dict of f32
+    device tensors in ``fdField``'s keys: ``None`` (= ``input`` = ``cloud``) the K kept points [K,3], ``normal`` [K,3] the cast
+    directions, ``len`` [K,3] the length repeated per component as the script writes it, plus ``index`` (the mesh) and ``keep``
+    (bool [num_rays]).  The draws (``u``, ``r1``, ``r2``, ``g``, ``w``, in this order) come from a device generator seeded by
+    (seed, epoch, item): deterministic, and not the reference's streams; ``last_draws`` holds them.  A mesh that is not watertight
+    raises ``ValueError`` when it is sampled, unless ``allow_open``."""
+
+    def __init__(self, meshes, num_rays=4096, split="train", shuffle=True, seed=0, device=None, allow_open=False):
+        if split not in ("train", "val", "all"):
+            raise ValueError("split must be 'train', 'val' or 'all'")
+        if int(num_rays) < 1:
+            raise ValueError("num_rays must be >= 1")
+        if isinstance(meshes, (str, os.PathLike)):
+            files = mesh_files(meshes)
+            lo, hi = split_range(len(files), split)
+            names = files[lo:hi]
+            pairs = [mesh_mod.read_off(f, triangulate=True) for f in names]
+            pairs = [(v.astype(np.float32), f) for v, f in pairs]
+        else:
+            meshes = list(meshes)
+            lo, hi = split_range(len(meshes), split)
+            names, pairs = ["mesh %d" % i for i in range(lo, hi)], meshes[lo:hi]
+        if hi <= lo:
+            raise ValueError("the %s split is empty" % split)
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("device %s: there is no CPU path" % dev)
+        self.split, self.device, self.num_rays = split, dev, int(num_rays)
+        self.shuffle, self.seed, self.epoch, self.allow_open = bool(shuffle), int(seed), 0, bool(allow_open)
+        self.last_draws = None
+        self.tables = surface.build_surface_tables(pairs, device=dev, names=names)
+
+    def __len__(self):
+        return len(self.tables)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+        return self
+
+    def _generator(self, item):
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(((self.seed * 1000003 + self.epoch) * 1000003 + item + 1) & (2 ** 63 - 1))
+        return gen
+
+    def sample(self, m, item=None):
+        """The item of mesh m of the split, from the generator of (seed, epoch, item); item None = m."""
+        gen = self._generator(int(m) if item is None else int(item))
+        n, dev = self.num_rays, self.device
+        u = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64)
+        r1 = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64).float()
+        r2 = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64).float()
+        g = torch.randn((n, 3), generator=gen, device=dev, dtype=torch.float64)
+        w = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64)
+        self.last_draws = {"u": u, "r1": r1, "r2": r2, "g": g, "w": w}
+        keep, points, normals, lens = ray_mod.sample_fd_rays(self.tables, int(m), u, r1, r2, g, w, allow_open=self.allow_open)
+        return {None: points, "input": points, "cloud": points, "normal": normals, "len": lens.reshape(-1, 1).repeat(1, 3),
+                "index": int(m), "keep": keep}
+
+    def __iter__(self):
+        S = len(self)
+        order = torch.randperm(S, generator=self._generator(-1), device=self.device).tolist() if self.shuffle else list(range(S))
+        for item, m in enumerate(order):
+            yield self.sample(m, item)
