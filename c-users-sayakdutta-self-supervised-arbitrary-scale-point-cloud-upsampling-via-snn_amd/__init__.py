@@ -15,6 +15,8 @@ Public surface = the reference's own interface for this path:
   build_surface_tables, sample_surface                        (``surface``: area-weighted sampling of triangle meshes on the device)
   ray_to_mesh, signed_ray_distance, ray_metrics,              (``ray``: ray casting against triangle meshes on the device, the ground
   sample_fd_rays, as_fd_npz, is_watertight, FdRayPatches       truth of fd's directed distance, fd's ray samples from meshes)
+  pca_normals, normal_angles, normal_metrics,                 (``normals``: PCA normals of a cloud and the angular error of normals
+  cloud_normal_metrics, evaluate_normals_file                  on the device: fn's score, ground-truth normals, surface quality)
 Importing the package never touches the GPU; the HIP library is loaded on first use and its
 absence raises ``SapcuLibraryError`` (no CPU fallback exists).
 """
@@ -28,6 +30,7 @@ from .mesh import point_to_mesh, mesh_metrics, mesh_dataset_metrics, read_off, e
 from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches, FdRayPatches  # noqa: F401
 from .surface import build_surface_tables, sample_surface  # noqa: F401
 from .ray import ray_to_mesh, signed_ray_distance, ray_metrics, sample_fd_rays, as_fd_npz, is_watertight  # noqa: F401
+from .normals import pca_normals, normal_angles, normal_metrics, cloud_normal_metrics, evaluate_normals_file  # noqa: F401
 
 __all__ = ["ImprovedSNNNormalEstimation", "EnhancedSNNDistanceEstimation", "TrainableSNNDistanceEstimation", "Generator3D6",
            "SNNPointCloudGenerator", "SapcuError", "SapcuLibraryError"]

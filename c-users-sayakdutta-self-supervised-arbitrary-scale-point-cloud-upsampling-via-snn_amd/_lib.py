@@ -185,6 +185,14 @@ _RAY_SIGNATURES = {
 }
 RAY_EXPORTS = tuple(_RAY_SIGNATURES)
 
+# include/sapcu_normals.h: PCA normals from a neighbour table and the angle between two tables of normals (a twelfth table);
+# viewpoint_host is a HOST double[3] or None
+_NORMALS_SIGNATURES = {
+    "sapcu_pca_normals_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sapcu_normal_angles_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+}
+NORMALS_EXPORTS = tuple(_NORMALS_SIGNATURES)
+
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
 _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -222,7 +230,7 @@ def load(path=None):
     for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
             list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
             list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_SURFACE_SIGNATURES.items()) + \
-            list(_SINKHORN_SIGNATURES.items()) + list(_RAY_SIGNATURES.items()) + \
+            list(_SINKHORN_SIGNATURES.items()) + list(_RAY_SIGNATURES.items()) + list(_NORMALS_SIGNATURES.items()) + \
             list(_INTERNAL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
