@@ -3,7 +3,7 @@
 //
 // Per level (a frontier of m voxel keys in the host's queue order):
 //   1. seeds_eval_kernel — one voxel per thread.  The 11 nearest of the n+1 points (the cloud plus the reference's all-zero point)
-//      by the shell search of knn_grid.hip on that file's cell grid, compared on (squared distance, index) keys; the squared
+//      by grid_shell_walk (knn_grid.h) on knn_grid.hip's cell grid, compared on (squared distance, index) keys; the squared
 //      distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 — the host's (0 + dx^2) + dy^2 + dz^2 (0 + a = a,
 //      (p-q)^2 = (q-p)^2 exactly).  The ten nearest in DESCENDING key order are the host heap's pop order: near[0..7] the fan,
 //      near[8], near[9] (the two nearest) the shared edge; fewer than 10 points leave zeros behind the ones found.  Then
@@ -240,33 +240,10 @@ __global__ __launch_bounds__(256) void seeds_eval_kernel(const int* __restrict__
             L.d[q] = INF;
             L.i[q] = 0x7fffffff;
         }
-        const int rmax = max(max(p.gx, p.gy), p.gz);
-        for (int r = 0; r <= rmax; ++r) {                              // the shells and the stop rule of knn_self_grid_kernel
-            const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
-            const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
-            const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
-            for (int zz = z0; zz <= z1; ++zz) {
-                for (int yy = y0; yy <= y1; ++yy) {
-                    const int row = (zz * p.gy + yy) * p.gx;
-                    if (zz == cz - r || zz == cz + r || yy == cy - r || yy == cy + r) {
-                        seed_scan_range(L, start[row + x0], start[row + x1 + 1], qx, qy, qz, sx, sy, sz, sidx);
-                    } else {
-                        if (cx - r >= 0) seed_scan_range(L, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, sx, sy, sz, sidx);
-                        if (cx + r < p.gx) seed_scan_range(L, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, sx, sy, sz, sidx);
-                    }
-                }
-            }
-            double bnd = INF;
-            if (cx - r > 0) bnd = fmin(bnd, qx - (p.ox + (double)(cx - r) * p.h));
-            if (cx + r < p.gx - 1) bnd = fmin(bnd, (p.ox + (double)(cx + r + 1) * p.h) - qx);
-            if (cy - r > 0) bnd = fmin(bnd, qy - (p.oy + (double)(cy - r) * p.h));
-            if (cy + r < p.gy - 1) bnd = fmin(bnd, (p.oy + (double)(cy + r + 1) * p.h) - qy);
-            if (cz - r > 0) bnd = fmin(bnd, qz - (p.oz + (double)(cz - r) * p.h));
-            if (cz + r < p.gz - 1) bnd = fmin(bnd, (p.oz + (double)(cz + r + 1) * p.h) - qz);
-            if (bnd == INF) break;
-            bnd = bnd - p.slack;
-            if (bnd > 0.0 && (bnd * bnd) * (1.0 - 1e-9) > L.d[SEED_NN - 1]) break;
-        }
+        grid_shell_walk(                                                // one voxel per thread: a per-thread stop rule
+            p, start, cx, cy, cz, qx, qy, qz, p.slack,
+            [&](int a, int b) { seed_scan_range(L, a, b, qx, qy, qz, sx, sy, sz, sidx); },
+            [&](double bnd) { return grid_bound_clears(bnd, L.d[SEED_NN - 1]); });
         // host recomputation: a tie at the boundary of the ten, or no table entry for x
         const bool tie = g.npts >= SEED_NN && L.d[SEED_NN - 2] == L.d[SEED_NN - 1];
         const bool off_table = x < -g.boxsize || x > 2 * g.boxsize;

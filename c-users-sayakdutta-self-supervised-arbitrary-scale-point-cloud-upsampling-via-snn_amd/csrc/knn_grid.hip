@@ -9,12 +9,8 @@
 //   * one query per wavefront (4 per 256-thread workgroup).  The running top-k is the sorted list of knn_outer.hip,
 //     distributed across the lanes (entry p in lane p, k <= 64); candidates arrive in cell order, not index order, so
 //     a candidate is compared on the key (d, i) — a point at the k-th distance with a lower index still enters;
-//   * the search visits Chebyshev shells r = 0, 1, 2, ... around the query's cell.  A shell row whose y or z offset
-//     is +-r is ONE contiguous range of the sorted points (the cells of a row are consecutive keys); the other rows
-//     contribute their two end cells.  After shell r the distance from the query to the faces of the visited block,
-//     less a slack far above the rounding of the cell keys and of the faces, bounds every unvisited point from below;
-//     the search stops only when that bound squared (shrunk by 1e-9) is STRICTLY above the current k-th squared
-//     distance — a point whose rounded distance ties the k-th cannot be skipped.  Correct for any cell size;
+//   * the search is grid_shell_walk (knn_grid.h: the shells, the lower bound after each and the stop rule), with GridParams.slack
+//     as the margin, against the current k-th squared distance;
 //   * the squared distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 operations, the output
 //     distance sqrt_cr of it: bit for bit the arithmetic and the order of knn_outer.hip;
 //   * non-finite or huge (|x| > 1e150) coordinates, and n < KNN_GRID_MIN_N with the automatic cell size, run the
@@ -282,36 +278,10 @@ __global__ __launch_bounds__(256) void knn_self_grid_kernel(const double* __rest
     const int cz = grid_coord(qz, p.oz, p.h, p.gz);
     const double INF = __builtin_huge_val();
     GridList L{INF, 0x7fffffff, INF, 0x7fffffff};
-    const int rmax = max(max(p.gx, p.gy), p.gz);
-    for (int r = 0; r <= rmax; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
-        for (int z = z0; z <= z1; ++z) {
-            for (int y = y0; y <= y1; ++y) {
-                const int row = (z * p.gy + y) * p.gx;
-                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {        // a face row of the shell: its whole x range
-                    grid_scan_range(L, start[row + x0], start[row + x1 + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
-                } else {                                                            // an inner row: its two end cells
-                    if (cx - r >= 0)
-                        grid_scan_range(L, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
-                    if (cx + r < p.gx)
-                        grid_scan_range(L, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, sx, sy, sz, sidx, k, lane);
-                }
-            }
-        }
-        // lower bound for every point outside the visited block [c-r, c+r]^3 (a side at the grid's edge has none)
-        double bnd = INF;
-        if (cx - r > 0) bnd = fmin(bnd, __dsub_rn(qx, __dadd_rn(p.ox, __dmul_rn((double)(cx - r), p.h))));
-        if (cx + r < p.gx - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.ox, __dmul_rn((double)(cx + r + 1), p.h)), qx));
-        if (cy - r > 0) bnd = fmin(bnd, __dsub_rn(qy, __dadd_rn(p.oy, __dmul_rn((double)(cy - r), p.h))));
-        if (cy + r < p.gy - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oy, __dmul_rn((double)(cy + r + 1), p.h)), qy));
-        if (cz - r > 0) bnd = fmin(bnd, __dsub_rn(qz, __dadd_rn(p.oz, __dmul_rn((double)(cz - r), p.h))));
-        if (cz + r < p.gz - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oz, __dmul_rn((double)(cz + r + 1), p.h)), qz));
-        if (bnd == INF) break;                                               // the whole grid is visited
-        bnd = __dsub_rn(bnd, p.slack);
-        if (bnd > 0.0 && __dmul_rn(__dmul_rn(bnd, bnd), 1.0 - 1e-9) > L.tau_d) break;
-    }
+    grid_shell_walk(
+        p, start, cx, cy, cz, qx, qy, qz, p.slack,
+        [&](int a, int b) { grid_scan_range(L, a, b, qx, qy, qz, sx, sy, sz, sidx, k, lane); },
+        [&](double bnd) { return grid_bound_clears(bnd, L.tau_d); });                      // against the k-th squared distance
     if (lane < k) {
         const int64_t o = (qi - row0) * k + lane;
         idx_out[o] = L.i;
@@ -371,6 +341,19 @@ int launch_grid_sort(const double* pts, int64_t n, const GridWs& w, const GridPa
     hipLaunchKernelGGL(grid_scatter_kernel, dim3(nb), dim3(256), 0, st, pts, n, w.key, w.cursor, w.sx, w.sy, w.sz, w.sidx);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
+}
+
+// wavefronts per cell: ceil(queries / 64); entry `cells` (the scan's total) starts at 0
+__global__ __launch_bounds__(256) void grid_query_waves_kernel(const int* __restrict__ qstart, int64_t cells, int* __restrict__ wstart) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c > cells) return;
+    wstart[c] = c < cells ? (qstart[c + 1] - qstart[c] + 63) >> 6 : 0;
+}
+
+int launch_grid_query_waves(const int* qstart, int64_t cells, int* wstart, int* tile_sums, hipStream_t st) {
+    hipLaunchKernelGGL(grid_query_waves_kernel, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, st, qstart, cells, wstart);
+    SAPCU_CHECK_LAUNCH();
+    return launch_exclusive_scan_int(wstart, cells + 1, tile_sums, st);
 }
 
 int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row1, int k, double cell_size, int64_t* idx,

@@ -1,6 +1,7 @@
 // What the translation units that work on triangle meshes share (mesh_dist.hip: the distance to a mesh; ray_cast.hip: ray casting):
-// the face record with its skip rule, the dot product in the definition's order, the counters of a call, and the launchers of the two
-// face passes that live in mesh_dist.hip (a kernel is launched from the file that defines it).
+// the face record with its skip rule, the dot product in the definition's order, the counters of a call, the per-wave LDS slab scan
+// of a range of faces, the argument checks and the brute-force route of the entry points, and the
+// launchers of the two face passes that live in mesh_dist.hip (a kernel is launched from the file that defines it).
 #pragma once
 #include "common.h"
 #include "knn_grid.h"
@@ -55,11 +56,73 @@ __device__ __forceinline__ MeshFace mesh_load_face(int f, const double* __restri
     return m;
 }
 
+// The records load(j), j in [a, b), against every lane's query: a wavefront gathers 64 records at a time into its own LDS slab (one per
+// lane, coalesced) and reads them back one at a time, all lanes at one address: a broadcast.  test(rec) runs in every lane for every
+// record with idx >= 0; a skipped face costs one wave-uniform branch.
+template <typename Rec, typename Load, typename Test>
+__device__ __forceinline__ void mesh_slab_scan(int a, int b, Rec* slab, int lane, Load load, Test test) {
+    for (int off = a; off < b; off += 64) {
+        const int j = off + lane;
+        Rec mine{};
+        mine.idx = -1;
+        if (j < b) mine = load(j);
+        __builtin_amdgcn_wave_barrier();
+        slab[lane] = mine;
+        __builtin_amdgcn_wave_barrier();
+        const int cnt = min(64, b - off);                                   // wave-uniform
+#pragma unroll 2
+        for (int t = 0; t < cnt; ++t) {
+            const Rec m = slab[t];
+            if (m.idx < 0) continue;                                        // wave-uniform
+            test(m);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- host side
+static inline bool mesh_sizes_ok(int64_t nv, int64_t nf, int64_t nq) {
+    return nv >= 1 && nv <= (1LL << 31) - 1 && nf >= 1 && nf <= (1LL << 29) && nq >= 0 && nq <= (1LL << 31) - 64;
+}
+
+// the argument checks of every entry point that takes a mesh and `nq` queries or rays (named `qname` in the messages); `need`: the
+// entry point's workspace size, read only once the sizes are in range
+static int mesh_args_check(const char* who, const char* qname, const void* vertices, int64_t nv, const void* faces, int64_t nf,
+                           bool rest_given, int64_t nq, double cell_size, void* workspace, int64_t workspace_bytes, int64_t need) {
+    SAPCU_CHECK_ARG(nv >= 1 && nv <= (1LL << 31) - 1, "%s: need 1 <= nv <= 2^31 - 1 (nv=%lld)", who, (long long)nv);
+    SAPCU_CHECK_ARG(nf >= 1 && nf <= (1LL << 29), "%s: need 1 <= nf <= 2^29 (nf=%lld)", who, (long long)nf);
+    SAPCU_CHECK_ARG(nq >= 0 && nq <= (1LL << 31) - 64, "%s: need 0 <= %s <= 2^31 - 64 (%s=%lld)", who, qname, qname, (long long)nq);
+    SAPCU_CHECK_ARG(vertices && faces && (rest_given || nq == 0), "%s: null pointer", who);       // no query: nothing is written
+    SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "%s: cell_size must be finite and >= 0", who);
+    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: the workspace must be 8-byte aligned (f64 tables)", who);
+    SAPCU_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes,
+                    (long long)need);
+    return SAPCU_OK;
+}
+
 // mesh_dist.hip: centroid c' = ((a + b) + c) / 3 and radius r_f = max |vertex - c'| * (1 + 1e-9) of every face, the skipped faces
 // counted into ctl->n_skip (centroid NULL: the count alone); the oversize list (radius above mult cell edges of prm) with its length in
 // ctl->n_over, and the bits of the largest radius of the other faces in ctl->rbits.  *ctl is zeroed by the caller.
 int launch_mesh_prep(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, double* centroid, double* radius, MeshCtl* ctl,
                      hipStream_t st);
 int launch_mesh_classify(const double* radius, int64_t nf, const GridParams* prm, double mult, int* olist, MeshCtl* ctl, hipStream_t st);
+
+// a call that goes straight to brute force, launched by brute(): the skipped faces are counted into info[5] (the face pass without
+// centroids, one read-back of *ctl) only for a caller who asks
+template <typename Brute>
+static int mesh_brute_route(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, MeshCtl* ctl, int64_t* info, hipStream_t st,
+                            Brute brute) {
+    if (info) {
+        SAPCU_CHECK_HIP(hipMemsetAsync(ctl, 0, sizeof(MeshCtl), st));
+        const int rc = launch_mesh_prep(vertices, nv, faces, nf, nullptr, nullptr, ctl, st);
+        if (rc != SAPCU_OK) return rc;
+    }
+    const int rc = brute();
+    if (rc != SAPCU_OK || !info) return rc;
+    MeshCtl hc;
+    SAPCU_CHECK_HIP(hipMemcpyAsync(&hc, ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
+    SAPCU_CHECK_HIP(hipStreamSynchronize(st));
+    info[5] = hc.n_skip;
+    return SAPCU_OK;
+}
 
 }  // namespace sapcu

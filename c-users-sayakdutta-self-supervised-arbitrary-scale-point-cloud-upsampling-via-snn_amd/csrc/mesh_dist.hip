@@ -12,7 +12,7 @@
 // faces at a time (three indices, nine coordinates, skipped faces flagged while loading) into its own LDS slab and reads them
 // back one face at a time, all lanes at one address: a broadcast.  Each lane keeps (d2, face, q) and compares on the key (d2, face).
 //
-// mesh_grid_kernel, the structure of metrics.hip's nn_cross_kernel:
+// mesh_grid_kernel, 64 queries of one cell per wavefront on grid_shell_walk (knn_grid.h: the query table, the walk, the stop rule):
 //   * mesh_prep_kernel writes the centroid c' = ((a + b) + c) / 3 of every face and its radius r_f = max |vertex - c'| * (1 + 1e-9);
 //     knn_grid.hip's launchers build the cell grid over the centroids and counting-sort the faces into it, then the queries by the
 //     (clamped) cell of that grid they fall in; a cell with c queries gets ceil(c / 64) wavefronts;
@@ -20,8 +20,8 @@
 //     c': the rounding of the centroid itself costs nothing.  The radius is computed from c' as stored; its rounding (three
 //     subtractions, a dot product and a square root: below 1e-15 relative) is covered by the factor 1 + 1e-9;
 //   * after shell r every unvisited in-grid face has its centroid in a cell outside the visited block, hence every point of it lies
-//     at least bnd - R away, R the largest radius among in-grid faces and bnd the distance to the block's faces.  A lane is
-//     satisfied when bnd - R - slack > 0 and its square, shrunk by 1 - 1e-9, is STRICTLY above the lane's best d2;
+//     at least bnd - R away, R the largest radius among in-grid faces and bnd the distance to the block's faces: the walk's margin
+//     is R + slack, its stop rule runs per lane against the lane's best d2, and the wave leaves when every lane is satisfied;
 //   * slack = GridParams.slack of the centroids' grid, 1e-11 * (|centroid|max + extent + h), which covers the rounding of the cell
 //     keys and of the block's face planes (about 1e-16 of the same magnitudes), plus 1e-11 * (largest |coordinate| of the vertices)
 //     plus 1e-11 * (largest |coordinate| of the queries): q - plane is rounded at the query's magnitude, and the vertices of an
@@ -36,7 +36,7 @@
 //     integer maximum over the bits of non-negative doubles), no scratch.
 // The brute-force kernel runs instead for non-finite or huge (|x| > 1e150) coordinates in vertices or queries, when more than
 // 1 / MESH_OVERSIZE_SHARE_DIV of the faces are oversize, and for nf < MESH_GRID_MIN_FACES with the automatic cell size.
-// The face record with its skip rule, mesh_dot and the counters live in mesh_common.h, which ray_cast.hip shares; it reaches
+// The face record with its skip rule, mesh_dot, the slab scan and the counters live in mesh_common.h, which ray_cast.hip shares; it reaches
 // mesh_prep_kernel and mesh_classify_kernel through launch_mesh_prep / launch_mesh_classify below.
 #include "mesh_common.h"
 #include "../../include/sapcu_mesh.h"
@@ -64,27 +64,16 @@ struct MeshWs {
 
 static MeshWs mesh_ws_layout(void* base, int64_t nf, int64_t nq) {
     const int64_t cap = grid_cell_cap(nf);
-    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
     MeshWs w;
     w.g = grid_ws_layout(base, nf);
     WsCarver c(base ? (char*)base + w.g.bytes : nullptr);
-    w.q.partials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
-    w.q.params = w.g.params;
-    w.q.start = c.take<int>(cap + 1);
-    w.q.cursor = c.take<int>(cap);
-    w.q.tile_sums = c.take<int>(tiles);
-    w.q.key = c.take<int>(nq);
-    w.q.sx = c.take<double>(nq);
-    w.q.sy = c.take<double>(nq);
-    w.q.sz = c.take<double>(nq);
-    w.q.sidx = c.take<int>(nq);
+    w.q = grid_query_ws_layout(c, cap, nq, w.g.params);
     w.vpartials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
     w.wstart = c.take<int>(cap + 1);
     w.centroid = c.take<double>(3 * nf);
     w.radius = c.take<double>(nf);
     w.olist = c.take<int>(nf);
     w.ctl = c.take<MeshCtl>(1);
-    w.q.bytes = c.bytes();
     w.bytes = w.g.bytes + c.bytes();
     return w;
 }
@@ -148,21 +137,9 @@ __device__ __forceinline__ void mesh_face_test(MeshBest& B, const MeshFace& m, d
 __device__ __forceinline__ void mesh_scan_range(MeshBest& B, int a, int b, const int* __restrict__ order, const double* __restrict__ vertices,
                                                 int64_t nv, const int32_t* __restrict__ faces, double px, double py, double pz,
                                                 MeshFace* slab, int lane) {
-    for (int off = a; off < b; off += 64) {
-        const int j = off + lane;
-        MeshFace mine{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -1, 0};
-        if (j < b) mine = mesh_load_face(order ? order[j] : j, vertices, nv, faces);
-        __builtin_amdgcn_wave_barrier();
-        slab[lane] = mine;
-        __builtin_amdgcn_wave_barrier();
-        const int cnt = min(64, b - off);                                   // wave-uniform
-#pragma unroll 2
-        for (int t = 0; t < cnt; ++t) {
-            const MeshFace m = slab[t];                                     // one address for the whole wave: a broadcast
-            if (m.idx < 0) continue;                                        // wave-uniform
-            mesh_face_test(B, m, px, py, pz);
-        }
-    }
+    mesh_slab_scan(
+        a, b, slab, lane, [&](int j) { return mesh_load_face(order ? order[j] : j, vertices, nv, faces); },
+        [&](const MeshFace& m) { mesh_face_test(B, m, px, py, pz); });
 }
 
 __device__ __forceinline__ void mesh_store(const MeshBest& B, int64_t o, double* __restrict__ dist_out, int64_t* __restrict__ face_out,
@@ -233,22 +210,9 @@ __global__ __launch_bounds__(256) void mesh_prep_kernel(const double* __restrict
 // one wavefront: the bad flags and magnitudes of the vertices and of the queries into the centroid grid's parameters (maxima: any order)
 __global__ __launch_bounds__(64) void mesh_setup_kernel(const double* __restrict__ vpartials, const double* __restrict__ qpartials,
                                                         GridParams* __restrict__ prm) {
-    double amax_v = 0.0, amax_q = 0.0, bad = 0.0;
-    for (int b = threadIdx.x; b < KNN_GRID_BBOX_BLOCKS; b += 64) {
-        const double* v = vpartials + b * 8;
-        const double* q = qpartials + b * 8;
-        bad = fmax(bad, fmax(v[6], q[6]));
-        for (int c = 0; c < 6; ++c) {                                       // a block without points holds +-inf
-            if (fabs(v[c]) <= 1e150) amax_v = fmax(amax_v, fabs(v[c]));
-            if (fabs(q[c]) <= 1e150) amax_q = fmax(amax_q, fabs(q[c]));
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        amax_v = fmax(amax_v, __shfl_xor(amax_v, o));
-        amax_q = fmax(amax_q, __shfl_xor(amax_q, o));
-        bad = fmax(bad, __shfl_xor(bad, o));
-    }
+    double amax_v, amax_q, bad = 0.0;
+    grid_partials_fold(vpartials, &amax_v, &bad);
+    grid_partials_fold(qpartials, &amax_q, &bad);
     if (threadIdx.x != 0) return;
     if (bad != 0.0) {
         prm->fallback = 1;
@@ -276,13 +240,6 @@ __global__ __launch_bounds__(256) void mesh_classify_kernel(const double* __rest
     if ((threadIdx.x & 63) == 0 && r > 0.0) atomicMax(&ctl->rbits, (unsigned long long)__double_as_longlong(r));
 }
 
-// wavefronts per cell: ceil(queries / 64); entry `cells` (the scan's total) starts at 0
-__global__ __launch_bounds__(256) void mesh_waves_kernel(const int* __restrict__ qstart, int64_t cells, int* __restrict__ wstart) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > cells) return;
-    wstart[c] = c < cells ? (qstart[c + 1] - qstart[c] + 63) >> 6 : 0;
-}
-
 __global__ __launch_bounds__(256) void mesh_grid_kernel(const GridParams* __restrict__ prm, const int* __restrict__ start,
                                                         const int* __restrict__ fsidx, const int* __restrict__ olist, int n_over, double R,
                                                         const double* __restrict__ vertices, int64_t nv, const int32_t* __restrict__ faces,
@@ -295,14 +252,8 @@ __global__ __launch_bounds__(256) void mesh_grid_kernel(const GridParams* __rest
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t w = (int64_t)blockIdx.x * MESH_WAVES + wave;
-    if (w >= (int64_t)wstart[cells]) return;                               // wave-uniform: beyond the last (cell, chunk)
-    int lo = 0, hi = cells;                                                 // wstart[lo] <= w < wstart[hi]
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)wstart[mid] <= w) lo = mid; else hi = mid;
-    }
-    const int cell = lo;
-    const int qa = qstart[cell] + ((int)w - wstart[cell]) * 64, qb = qstart[cell + 1];
+    int cell, qa, qb;
+    if (!grid_wave_chunk(w, wstart, qstart, cells, &cell, &qa, &qb)) return;
     const bool valid = qa + lane < qb;
     const int j = valid ? qa + lane : qa;                                   // a spare lane repeats the chunk's first query
     const double px = qsx[j], py = qsy[j], pz = qsz[j];
@@ -312,39 +263,10 @@ __global__ __launch_bounds__(256) void mesh_grid_kernel(const GridParams* __rest
     MeshBest B{INF, -1, 0.0, 0.0, 0.0};
     MeshFace* slab = slabs[wave];
     mesh_scan_range(B, 0, n_over, olist, vertices, nv, faces, px, py, pz, slab, lane);
-    const double margin = __dadd_rn(R, p.slack);
-    const int rmax = max(max(p.gx, p.gy), p.gz);
-    for (int r = 0; r <= rmax; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
-        for (int z = z0; z <= z1; ++z) {
-            for (int y = y0; y <= y1; ++y) {
-                const int row = (z * p.gy + y) * p.gx;
-                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {        // a face row of the shell: its whole x range
-                    mesh_scan_range(B, start[row + x0], start[row + x1 + 1], fsidx, vertices, nv, faces, px, py, pz, slab, lane);
-                } else {                                                            // an inner row: its two end cells
-                    if (cx - r >= 0)
-                        mesh_scan_range(B, start[row + cx - r], start[row + cx - r + 1], fsidx, vertices, nv, faces, px, py, pz, slab, lane);
-                    if (cx + r < p.gx)
-                        mesh_scan_range(B, start[row + cx + r], start[row + cx + r + 1], fsidx, vertices, nv, faces, px, py, pz, slab, lane);
-                }
-            }
-        }
-        // each lane's lower bound for every centroid outside the visited block [c-r, c+r]^3 (a side at the grid's edge has none)
-        double bnd = INF;
-        if (cx - r > 0) bnd = fmin(bnd, __dsub_rn(px, __dadd_rn(p.ox, __dmul_rn((double)(cx - r), p.h))));
-        if (cx + r < p.gx - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.ox, __dmul_rn((double)(cx + r + 1), p.h)), px));
-        if (cy - r > 0) bnd = fmin(bnd, __dsub_rn(py, __dadd_rn(p.oy, __dmul_rn((double)(cy - r), p.h))));
-        if (cy + r < p.gy - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oy, __dmul_rn((double)(cy + r + 1), p.h)), py));
-        if (cz - r > 0) bnd = fmin(bnd, __dsub_rn(pz, __dadd_rn(p.oz, __dmul_rn((double)(cz - r), p.h))));
-        if (cz + r < p.gz - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oz, __dmul_rn((double)(cz + r + 1), p.h)), pz));
-        if (cx - r <= 0 && cx + r >= p.gx - 1 && cy - r <= 0 && cy + r >= p.gy - 1 && cz - r <= 0 && cz + r >= p.gz - 1)
-            break;                                                           // the whole grid is visited (wave-uniform)
-        bnd = __dsub_rn(bnd, margin);                                        // a face reaches R from its centroid
-        const bool open = !(bnd > 0.0 && __dmul_rn(__dmul_rn(bnd, bnd), 1.0 - 1e-9) > B.d);
-        if (__ballot(open) == 0ull) break;                                   // every lane's bound is strictly above its best
-    }
+    grid_shell_walk(
+        p, start, cx, cy, cz, px, py, pz, __dadd_rn(R, p.slack),                           // a face reaches R from its centroid
+        [&](int a, int b) { mesh_scan_range(B, a, b, fsidx, vertices, nv, faces, px, py, pz, slab, lane); },
+        [&](double bnd) { return __ballot(!grid_bound_clears(bnd, B.d)) == 0ull; });       // every lane's bound clears its best
     if (valid) mesh_store(B, qsidx[j], dist_out, face_out, closest_out);
 }
 
@@ -381,22 +303,9 @@ int launch_point_mesh(const double* vertices, int64_t nv, const int32_t* faces, 
     const MeshWs w = mesh_ws_layout(ws, nf, nq);
     const unsigned fblocks = (unsigned)((nf + 255) / 256);
     MeshCtl hc{0ull, 0, 0};
-    if (force_brute || (cell_size == 0.0 && nf < MESH_GRID_MIN_FACES)) {
-        if (info) {                                                         // the skipped faces are counted only for a caller who asks
-            SAPCU_CHECK_HIP(hipMemsetAsync(w.ctl, 0, sizeof(MeshCtl), st));
-            hipLaunchKernelGGL(mesh_prep_kernel, dim3(fblocks), dim3(256), 0, st, vertices, nv, faces, (int)nf, (double*)nullptr,
-                               (double*)nullptr, w.ctl);
-            SAPCU_CHECK_LAUNCH();
-        }
-        const int rc = launch_mesh_brute(vertices, nv, faces, nf, queries, nq, dist, face, closest, st);
-        if (rc != SAPCU_OK) return rc;
-        if (info) {
-            SAPCU_CHECK_HIP(hipMemcpyAsync(&hc, w.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-            SAPCU_CHECK_HIP(hipStreamSynchronize(st));
-            info[5] = hc.n_skip;
-        }
-        return SAPCU_OK;
-    }
+    if (force_brute || (cell_size == 0.0 && nf < MESH_GRID_MIN_FACES))
+        return mesh_brute_route(vertices, nv, faces, nf, w.ctl, info, st,
+                                [&] { return launch_mesh_brute(vertices, nv, faces, nf, queries, nq, dist, face, closest, st); });
     SAPCU_CHECK_HIP(hipMemsetAsync(w.ctl, 0, sizeof(MeshCtl), st));
     int rc = launch_grid_bbox(vertices, nv, w.vpartials, st);
     if (rc != SAPCU_OK) return rc;
@@ -432,12 +341,9 @@ int launch_point_mesh(const double* vertices, int64_t nv, const int32_t* faces, 
     rc = launch_grid_sort(queries, nq, w.q, hp, st);                        // the faces' parameters: the faces' cells
     if (rc != SAPCU_OK) return rc;
     const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
-    hipLaunchKernelGGL(mesh_waves_kernel, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, st, w.q.start, cells, w.wstart);
-    SAPCU_CHECK_LAUNCH();
-    rc = launch_exclusive_scan_int(w.wstart, cells + 1, w.q.tile_sums, st);
+    rc = launch_grid_query_waves(w.q.start, cells, w.wstart, w.q.tile_sums, st);
     if (rc != SAPCU_OK) return rc;
-    const int64_t waves = (nq + 63) / 64 + (cells < nq ? cells : nq);       // >= sum of ceil(count / 64): nothing is read back
-    const int64_t grid = (waves + MESH_WAVES - 1) / MESH_WAVES;
+    const int64_t grid = (grid_query_wave_bound(nq, cells) + MESH_WAVES - 1) / MESH_WAVES;
     hipLaunchKernelGGL(mesh_grid_kernel, dim3((unsigned)grid), dim3(256), 0, st, w.g.params, w.g.start, w.g.sidx, w.olist, hc.n_over, R,
                        vertices, nv, faces, w.q.start, w.wstart, w.q.sx, w.q.sy, w.q.sz, w.q.sidx, (int)cells, dist, face, closest);
     SAPCU_CHECK_LAUNCH();
@@ -449,31 +355,17 @@ int launch_point_mesh(const double* vertices, int64_t nv, const int32_t* faces, 
 // ================================================================================== C ABI
 using namespace sapcu;
 
-static int mesh_check(const char* who, const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, const double* queries,
-                      int64_t nq, double cell_size, double* dist_out, void* workspace, int64_t workspace_bytes) {
-    SAPCU_CHECK_ARG(nv >= 1 && nv <= (1LL << 31) - 1, "%s: need 1 <= nv <= 2^31 - 1 (nv=%lld)", who, (long long)nv);
-    SAPCU_CHECK_ARG(nf >= 1 && nf <= (1LL << 29), "%s: need 1 <= nf <= 2^29 (nf=%lld)", who, (long long)nf);
-    SAPCU_CHECK_ARG(nq >= 0 && nq <= (1LL << 31) - 64, "%s: need 0 <= nq <= 2^31 - 64 (nq=%lld)", who, (long long)nq);
-    SAPCU_CHECK_ARG(vertices && faces && ((queries && dist_out) || nq == 0), "%s: null pointer", who);   // no query: nothing is written
-    SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "%s: cell_size must be finite and >= 0", who);
-    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: the workspace must be 8-byte aligned (f64 tables)", who);
-    const int64_t need = (int64_t)mesh_ws_layout(nullptr, nf, nq).bytes;
-    SAPCU_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes,
-                    (long long)need);
-    return SAPCU_OK;
-}
-
 extern "C" {
 
 int64_t sapcu_point_mesh_workspace_bytes(int64_t nv, int64_t nf, int64_t nq) {
-    if (nv < 1 || nv > (1LL << 31) - 1 || nf < 1 || nf > (1LL << 29) || nq < 0 || nq > (1LL << 31) - 64) return -1;
-    return (int64_t)mesh_ws_layout(nullptr, nf, nq).bytes;
+    return mesh_sizes_ok(nv, nf, nq) ? (int64_t)mesh_ws_layout(nullptr, nf, nq).bytes : -1;
 }
 
 int sapcu_point_mesh_f64(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, const double* queries, int64_t nq,
                          double cell_size, double* dist_out, int64_t* face_out, double* closest_out, void* workspace,
                          int64_t workspace_bytes, int64_t* info_host, void* stream) {
-    const int rc = mesh_check("point_mesh", vertices, nv, faces, nf, queries, nq, cell_size, dist_out, workspace, workspace_bytes);
+    const int rc = mesh_args_check("point_mesh", "nq", vertices, nv, faces, nf, queries && dist_out, nq, cell_size, workspace, workspace_bytes,
+                                   sapcu_point_mesh_workspace_bytes(nv, nf, nq));
     if (rc != SAPCU_OK) return rc;
     return launch_point_mesh(vertices, nv, faces, nf, queries, nq, cell_size, MESH_OVERSIZE_MULT, MESH_CELL_POP, false, dist_out,
                              face_out, closest_out, workspace, info_host, (hipStream_t)stream);
@@ -484,7 +376,8 @@ int sapcu_point_mesh_f64(const double* vertices, int64_t nv, const int32_t* face
 int sapcu_internal_point_mesh_tuned(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, const double* queries, int64_t nq,
                                     double cell_size, double oversize_mult, int cell_pop, int force_brute, double* dist_out,
                                     int64_t* face_out, double* closest_out, void* workspace, int64_t workspace_bytes, int64_t* info_host, void* stream) {
-    const int rc = mesh_check("point_mesh_tuned", vertices, nv, faces, nf, queries, nq, cell_size, dist_out, workspace, workspace_bytes);
+    const int rc = mesh_args_check("point_mesh_tuned", "nq", vertices, nv, faces, nf, queries && dist_out, nq, cell_size, workspace,
+                                   workspace_bytes, sapcu_point_mesh_workspace_bytes(nv, nf, nq));
     if (rc != SAPCU_OK) return rc;
     SAPCU_CHECK_ARG(oversize_mult > 0.0 && oversize_mult < 1e300 && cell_pop >= 1 && cell_pop <= 4096,
                     "point_mesh_tuned: need a positive finite oversize cap and 1 <= cell population <= 4096");

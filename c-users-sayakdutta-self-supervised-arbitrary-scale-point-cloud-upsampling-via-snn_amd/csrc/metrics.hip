@@ -5,21 +5,19 @@
 // nn_cross_kernel, one query per lane:
 //   * the grid is built over the cloud by knn_grid.hip's launchers (bounding box, counting sort into the cell-ordered SoA copy);
 //   * the queries are counting-sorted by the (clamped) cell of the CLOUD's grid they fall in, with the same launchers;
-//   * a cell with c queries gets ceil(c / 64) wavefronts: the exclusive scan of those counts is searched by wave w (binary search)
-//     for its (cell, chunk); the launch is the upper bound ceil(nq / 64) + min(cells, nq) waves, the ones beyond the total exit;
-//   * all lanes of a wave share one cell, so the Chebyshev-shell walk of knn_self_grid_kernel, its ranges start[..] and its loop
-//     bounds are wave-uniform.  A range is read 64 points at a time, coalesced, into the wave's own LDS slab; every point is then
+//   * a cell with c queries gets ceil(c / 64) wavefronts (knn_grid.h: launch_grid_query_waves scans those counts, grid_wave_chunk
+//     finds wave w's (cell, chunk); the launch is grid_query_wave_bound, the waves beyond the total exit);
+//   * all lanes of a wave share one cell, so grid_shell_walk (knn_grid.h), its ranges start[..] and its loop bounds are
+//     wave-uniform.  A range is read 64 points at a time, coalesced, into the wave's own LDS slab; every point is then
 //     read back by all lanes at once (one address: an LDS broadcast) and tested against each lane's own query.  A lane keeps
 //     (best d, best index) in registers and compares on the key (d, index): candidates arrive in cell order;
 //   * the squared distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 operations, the output sqrt_cr of it,
 //     the lowest index among equal distances: bit for bit knn_outer.hip at k = 1;
-//   * after shell r each lane evaluates the stop rule of knn_self_grid_kernel for its own position (face distance less slack,
-//     squared, shrunk by 1 - 1e-9, STRICTLY above its best); the wave leaves when every lane is satisfied.  A lane that was
-//     satisfied earlier goes on computing: a minimum over more candidates is still the minimum;
+//   * after shell r each lane evaluates the walk's stop rule for its own position against its own best; the wave leaves when
+//     every lane is satisfied.  A lane that was satisfied earlier goes on computing: a minimum over more candidates is still
+//     the minimum;
 //   * the slack covers the queries as well: GridParams.slack is sized to the cloud's coordinates, and a query 1e6 extents outside
-//     the box rounds q - face far above it.  nn_cross_setup_kernel adds 1e-11 * (largest |coordinate| of the queries' bounding box).
-//     The clamped cell of an outside query needs nothing more: a face plane still bounds everything beyond it from below, and a
-//     side at the grid's edge has nothing beyond it;
+//     the box rounds q - face far above it.  nn_cross_setup_kernel adds 1e-11 * (largest |coordinate| of the queries' bounding box);
 //   * results go to the queries' original positions with ordinary vector stores.  No float atomics, no scratch.
 // Non-finite or huge (|x| > 1e150) coordinates in either set, and n < KNN_GRID_MIN_N with the automatic cell size, run the
 // brute-force kernel of knn_outer.hip instead.
@@ -44,49 +42,26 @@ struct CrossWs {
 
 static CrossWs cross_ws_layout(void* base, int64_t n, int64_t nq) {
     const int64_t cap = grid_cell_cap(n);
-    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
     CrossWs w;
     w.g = grid_ws_layout(base, n);
     WsCarver c(base ? (char*)base + w.g.bytes : nullptr);
-    w.q.partials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
-    w.q.params = w.g.params;
-    w.q.start = c.take<int>(cap + 1);
-    w.q.cursor = c.take<int>(cap);
-    w.q.tile_sums = c.take<int>(tiles);
-    w.q.key = c.take<int>(nq);
-    w.q.sx = c.take<double>(nq);
-    w.q.sy = c.take<double>(nq);
-    w.q.sz = c.take<double>(nq);
-    w.q.sidx = c.take<int>(nq);
+    w.q = grid_query_ws_layout(c, cap, nq, w.g.params);
     w.wstart = c.take<int>(cap + 1);
     w.brute_idx = (int64_t*)w.q.sx;
-    w.q.bytes = c.bytes();
     w.bytes = w.g.bytes + c.bytes();
     return w;
 }
 
-// one thread: the queries' bad flag and magnitude into the cloud's grid parameters
-__global__ void nn_cross_setup_kernel(const double* __restrict__ qpartials, GridParams* __restrict__ prm) {
+// one wavefront: the queries' bad flag and magnitude into the cloud's grid parameters
+__global__ __launch_bounds__(64) void nn_cross_setup_kernel(const double* __restrict__ qpartials, GridParams* __restrict__ prm) {
+    double amax, bad = 0.0;
+    grid_partials_fold(qpartials, &amax, &bad);
     if (threadIdx.x != 0) return;
-    double amax = 0.0, bad = 0.0;
-    for (int b = 0; b < KNN_GRID_BBOX_BLOCKS; ++b) {
-        const double* q = qpartials + b * 8;
-        bad = fmax(bad, q[6]);
-        for (int c = 0; c < 6; ++c)
-            if (fabs(q[c]) <= 1e150) amax = fmax(amax, fabs(q[c]));        // a block without points holds +-inf
-    }
     if (bad != 0.0) {
         prm->fallback = 1;
         return;
     }
     prm->slack = __dadd_rn(prm->slack, __dmul_rn(1e-11, amax));
-}
-
-// wavefronts per cell: ceil(queries / 64); entry `cells` (the scan's total) starts at 0
-__global__ __launch_bounds__(256) void nn_cross_waves_kernel(const int* __restrict__ qstart, int64_t cells, int* __restrict__ wstart) {
-    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c > cells) return;
-    wstart[c] = c < cells ? (qstart[c + 1] - qstart[c] + 63) >> 6 : 0;
 }
 
 struct __align__(16) CrossPt {
@@ -144,14 +119,8 @@ __global__ __launch_bounds__(256) void nn_cross_kernel(const GridParams* __restr
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t w = (int64_t)blockIdx.x * NN_CROSS_WAVES + wave;
-    if (w >= (int64_t)wstart[cells]) return;                               // wave-uniform: beyond the last (cell, chunk)
-    int lo = 0, hi = cells;                                                 // wstart[lo] <= w < wstart[hi]
-    while (hi - lo > 1) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if ((int64_t)wstart[mid] <= w) lo = mid; else hi = mid;
-    }
-    const int cell = lo;
-    const int qa = qstart[cell] + ((int)w - wstart[cell]) * 64, qb = qstart[cell + 1];
+    int cell, qa, qb;
+    if (!grid_wave_chunk(w, wstart, qstart, cells, &cell, &qa, &qb)) return;
     const bool valid = qa + lane < qb;
     const int j = valid ? qa + lane : qa;                                   // a spare lane repeats the chunk's first query
     const double qx = qsx[j], qy = qsy[j], qz = qsz[j];
@@ -160,38 +129,10 @@ __global__ __launch_bounds__(256) void nn_cross_kernel(const GridParams* __restr
     const double INF = __builtin_huge_val();
     CrossBest B{INF, 0x7fffffff};
     CrossPt* slab = slabs[wave];
-    const int rmax = max(max(p.gx, p.gy), p.gz);
-    for (int r = 0; r <= rmax; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, p.gz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, p.gy - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, p.gx - 1);
-        for (int z = z0; z <= z1; ++z) {
-            for (int y = y0; y <= y1; ++y) {
-                const int row = (z * p.gy + y) * p.gx;
-                if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {        // a face row of the shell: its whole x range
-                    cross_scan_range(B, start[row + x0], start[row + x1 + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
-                } else {                                                            // an inner row: its two end cells
-                    if (cx - r >= 0)
-                        cross_scan_range(B, start[row + cx - r], start[row + cx - r + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
-                    if (cx + r < p.gx)
-                        cross_scan_range(B, start[row + cx + r], start[row + cx + r + 1], qx, qy, qz, sx, sy, sz, sidx, slab, lane);
-                }
-            }
-        }
-        // each lane's lower bound for every point outside the visited block [c-r, c+r]^3 (a side at the grid's edge has none)
-        double bnd = INF;
-        if (cx - r > 0) bnd = fmin(bnd, __dsub_rn(qx, __dadd_rn(p.ox, __dmul_rn((double)(cx - r), p.h))));
-        if (cx + r < p.gx - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.ox, __dmul_rn((double)(cx + r + 1), p.h)), qx));
-        if (cy - r > 0) bnd = fmin(bnd, __dsub_rn(qy, __dadd_rn(p.oy, __dmul_rn((double)(cy - r), p.h))));
-        if (cy + r < p.gy - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oy, __dmul_rn((double)(cy + r + 1), p.h)), qy));
-        if (cz - r > 0) bnd = fmin(bnd, __dsub_rn(qz, __dadd_rn(p.oz, __dmul_rn((double)(cz - r), p.h))));
-        if (cz + r < p.gz - 1) bnd = fmin(bnd, __dsub_rn(__dadd_rn(p.oz, __dmul_rn((double)(cz + r + 1), p.h)), qz));
-        if (cx - r <= 0 && cx + r >= p.gx - 1 && cy - r <= 0 && cy + r >= p.gy - 1 && cz - r <= 0 && cz + r >= p.gz - 1)
-            break;                                                           // the whole grid is visited (wave-uniform)
-        bnd = __dsub_rn(bnd, p.slack);
-        const bool open = !(bnd > 0.0 && __dmul_rn(__dmul_rn(bnd, bnd), 1.0 - 1e-9) > B.d);
-        if (__ballot(open) == 0ull) break;                                   // every lane's bound is strictly above its best
-    }
+    grid_shell_walk(
+        p, start, cx, cy, cz, qx, qy, qz, p.slack,
+        [&](int a, int b) { cross_scan_range(B, a, b, qx, qy, qz, sx, sy, sz, sidx, slab, lane); },
+        [&](double bnd) { return __ballot(!grid_bound_clears(bnd, B.d)) == 0ull; });       // every lane's bound clears its best
     if (valid) {
         const int o = qsidx[j];
         dist_out[o] = sqrt_cr(B.d);
@@ -227,12 +168,9 @@ int launch_nn_cross(const double* cloud, int64_t n, const double* queries, int64
     rc = launch_grid_sort(queries, nq, w.q, hp, st);                        // the cloud's parameters: the cloud's cells
     if (rc != SAPCU_OK) return rc;
     const int64_t cells = (int64_t)hp.gx * hp.gy * hp.gz;
-    hipLaunchKernelGGL(nn_cross_waves_kernel, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, st, w.q.start, cells, w.wstart);
-    SAPCU_CHECK_LAUNCH();
-    rc = launch_exclusive_scan_int(w.wstart, cells + 1, w.q.tile_sums, st);
+    rc = launch_grid_query_waves(w.q.start, cells, w.wstart, w.q.tile_sums, st);
     if (rc != SAPCU_OK) return rc;
-    const int64_t waves = (nq + 63) / 64 + (cells < nq ? cells : nq);       // >= sum of ceil(count / 64): nothing is read back
-    const int64_t grid = (waves + NN_CROSS_WAVES - 1) / NN_CROSS_WAVES;
+    const int64_t grid = (grid_query_wave_bound(nq, cells) + NN_CROSS_WAVES - 1) / NN_CROSS_WAVES;
     hipLaunchKernelGGL(nn_cross_kernel, dim3((unsigned)grid), dim3(256), 0, st, w.g.params, w.g.start, w.g.sx, w.g.sy, w.g.sz, w.g.sidx,
                        w.q.start, w.wstart, w.q.sx, w.q.sy, w.q.sz, w.q.sidx, (int)cells, dist, idx);
     SAPCU_CHECK_LAUNCH();

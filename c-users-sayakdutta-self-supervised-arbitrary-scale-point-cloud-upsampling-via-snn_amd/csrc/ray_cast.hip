@@ -9,7 +9,7 @@
 //
 // ray_brute_kernel, the definition on the device and the oracle of the grid route: one ray per lane; a wavefront gathers 64 faces at
 // a time (skipped faces flagged while loading) into its own LDS slab and reads them back one face at a time, all lanes at one
-// address: a broadcast.
+// address: a broadcast (mesh_common.h: mesh_slab_scan, shared with mesh_dist.hip).
 //
 // ray_grid_kernel, on the centroid grid of mesh_dist.hip (mesh_common.h: the same centroids, radii r_f, oversize list, largest
 // in-grid radius R):
@@ -80,21 +80,10 @@ struct RayWs {
 };
 
 static RayWs ray_ws_layout(void* base, int64_t nf, int64_t nq) {
-    const int64_t cap = grid_cell_cap(nf);
-    const int64_t tiles = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE;
     RayWs w;
     w.g = grid_ws_layout(base, nf);
     WsCarver c(base ? (char*)base + w.g.bytes : nullptr);
-    w.q.partials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
-    w.q.params = w.g.params;
-    w.q.start = c.take<int>(cap + 1);
-    w.q.cursor = c.take<int>(cap);
-    w.q.tile_sums = c.take<int>(tiles);
-    w.q.key = c.take<int>(nq);
-    w.q.sx = c.take<double>(nq);
-    w.q.sy = c.take<double>(nq);
-    w.q.sz = c.take<double>(nq);
-    w.q.sidx = c.take<int>(nq);
+    w.q = grid_query_ws_layout(c, grid_cell_cap(nf), nq, w.g.params);
     w.vpartials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
     w.dpartials = c.take<double>(8 * KNN_GRID_BBOX_BLOCKS);
     w.centroid = c.take<double>(3 * nf);
@@ -105,7 +94,6 @@ static RayWs ray_ws_layout(void* base, int64_t nf, int64_t nq) {
     w.t1 = c.take<double>(nq);
     w.np = c.take<int>(nq);
     w.ctl = c.take<RayCtl>(1);
-    w.q.bytes = c.bytes();
     w.bytes = w.g.bytes + c.bytes();
     return w;
 }
@@ -201,21 +189,9 @@ __device__ __forceinline__ void ray_face_test(RayBest& B, const RayFace& m, cons
 // the faces order[a..b) (order NULL: the faces a..b themselves) against every lane's ray
 __device__ __forceinline__ void ray_scan_range(RayBest& B, int a, int b, const int* __restrict__ order, const double* __restrict__ vertices,
                                                int64_t nv, const int32_t* __restrict__ faces, const Ray& r, RayFace* slab, int lane) {
-    for (int off = a; off < b; off += 64) {
-        const int j = off + lane;
-        RayFace mine{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -1, 0};
-        if (j < b) mine = ray_load_face(order ? order[j] : j, vertices, nv, faces);
-        __builtin_amdgcn_wave_barrier();
-        slab[lane] = mine;
-        __builtin_amdgcn_wave_barrier();
-        const int cnt = min(64, b - off);                                   // wave-uniform
-#pragma unroll 2
-        for (int t = 0; t < cnt; ++t) {
-            const RayFace m = slab[t];                                      // one address for the whole wave: a broadcast
-            if (m.idx < 0) continue;                                        // wave-uniform
-            ray_face_test(B, m, r);
-        }
-    }
+    mesh_slab_scan(
+        a, b, slab, lane, [&](int j) { return ray_load_face(order ? order[j] : j, vertices, nv, faces); },
+        [&](const RayFace& m) { ray_face_test(B, m, r); });
 }
 
 __device__ __forceinline__ void ray_store(const RayBest& B, const Ray& r, int64_t o, double* __restrict__ t_out, int64_t* __restrict__ face_out,
@@ -254,16 +230,13 @@ __global__ __launch_bounds__(64) void ray_setup_kernel(const double* __restrict_
                                                        const double* __restrict__ dpartials, GridParams* __restrict__ prm,
                                                        RayCtl* __restrict__ ctl) {
     const double INF = __builtin_huge_val();
-    double amax_v = 0.0, amax_o = 0.0, bad = 0.0;
+    double amax_v, amax_o, bad = 0.0;
+    grid_partials_fold(vpartials, &amax_v, &bad);
+    grid_partials_fold(opartials, &amax_o, &bad);
+    grid_partials_fold(dpartials, nullptr, &bad);                            // the directions: the bad flag alone
     double lo[3] = {INF, INF, INF}, hi[3] = {-INF, -INF, -INF};
     for (int b = threadIdx.x; b < KNN_GRID_BBOX_BLOCKS; b += 64) {
         const double* v = vpartials + b * 8;
-        const double* o = opartials + b * 8;
-        bad = fmax(bad, fmax(fmax(v[6], o[6]), dpartials[b * 8 + 6]));
-        for (int c = 0; c < 6; ++c) {                                       // a block without points holds +-inf
-            if (fabs(v[c]) <= 1e150) amax_v = fmax(amax_v, fabs(v[c]));
-            if (fabs(o[c]) <= 1e150) amax_o = fmax(amax_o, fabs(o[c]));
-        }
         for (int c = 0; c < 3; ++c) {
             lo[c] = fmin(lo[c], v[c]);
             hi[c] = fmax(hi[c], v[3 + c]);
@@ -271,9 +244,6 @@ __global__ __launch_bounds__(64) void ray_setup_kernel(const double* __restrict_
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        amax_v = fmax(amax_v, __shfl_xor(amax_v, o));
-        amax_o = fmax(amax_o, __shfl_xor(amax_o, o));
-        bad = fmax(bad, __shfl_xor(bad, o));
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             lo[c] = fmin(lo[c], __shfl_xor(lo[c], o));
@@ -474,21 +444,9 @@ static int launch_ray_mesh(const double* vertices, int64_t nv, const int32_t* fa
     const RayWs w = ray_ws_layout(ws, nf, nq);
     RayCtl hc;
     memset(&hc, 0, sizeof(hc));
-    if (route == RAY_ROUTE_BRUTE || (route == RAY_ROUTE_AUTO && cell_size == 0.0 && nf < RAY_GRID_MIN_FACES)) {
-        if (info) {                                                         // the skipped faces are counted only for a caller who asks
-            SAPCU_CHECK_HIP(hipMemsetAsync(w.ctl, 0, sizeof(RayCtl), st));
-            const int rc = launch_mesh_prep(vertices, nv, faces, nf, nullptr, nullptr, &w.ctl->m, st);
-            if (rc != SAPCU_OK) return rc;
-        }
-        const int rc = launch_ray_brute(vertices, nv, faces, nf, origins, dirs, t_max, nq, t, face, hit, st);
-        if (rc != SAPCU_OK) return rc;
-        if (info) {
-            SAPCU_CHECK_HIP(hipMemcpyAsync(&hc, w.ctl, sizeof(hc), hipMemcpyDeviceToHost, st));
-            SAPCU_CHECK_HIP(hipStreamSynchronize(st));
-            info[5] = hc.m.n_skip;
-        }
-        return SAPCU_OK;
-    }
+    if (route == RAY_ROUTE_BRUTE || (route == RAY_ROUTE_AUTO && cell_size == 0.0 && nf < RAY_GRID_MIN_FACES))
+        return mesh_brute_route(vertices, nv, faces, nf, &w.ctl->m, info, st,
+                                [&] { return launch_ray_brute(vertices, nv, faces, nf, origins, dirs, t_max, nq, t, face, hit, st); });
     SAPCU_CHECK_HIP(hipMemsetAsync(w.ctl, 0, sizeof(RayCtl), st));
     int rc = launch_grid_bbox(vertices, nv, w.vpartials, st);
     if (rc != SAPCU_OK) return rc;
@@ -544,52 +502,33 @@ static int launch_ray_mesh(const double* vertices, int64_t nv, const int32_t* fa
 // ================================================================================== C ABI
 using namespace sapcu;
 
-static bool ray_sizes_ok(int64_t nv, int64_t nf, int64_t nq) {
-    return nv >= 1 && nv <= (1LL << 31) - 1 && nf >= 1 && nf <= (1LL << 29) && nq >= 0 && nq <= (1LL << 31) - 64;
-}
-
-static int ray_check(const char* who, const void* vertices, int64_t nv, const void* faces, int64_t nf, bool rays_given, int64_t nq,
-                     double cell_size, void* workspace, int64_t workspace_bytes, int64_t need) {
-    SAPCU_CHECK_ARG(nv >= 1 && nv <= (1LL << 31) - 1, "%s: need 1 <= nv <= 2^31 - 1 (nv=%lld)", who, (long long)nv);
-    SAPCU_CHECK_ARG(nf >= 1 && nf <= (1LL << 29), "%s: need 1 <= nf <= 2^29 (nf=%lld)", who, (long long)nf);
-    SAPCU_CHECK_ARG(nq >= 0 && nq <= (1LL << 31) - 64, "%s: need 0 <= n <= 2^31 - 64 (n=%lld)", who, (long long)nq);
-    SAPCU_CHECK_ARG(vertices && faces && (rays_given || nq == 0), "%s: null pointer", who);       // no ray: nothing is written
-    SAPCU_CHECK_ARG(cell_size >= 0.0 && cell_size < 1e300, "%s: cell_size must be finite and >= 0", who);
-    SAPCU_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: the workspace must be 8-byte aligned (f64 tables)", who);
-    SAPCU_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace of %lld bytes, need %lld", who, (long long)workspace_bytes,
-                    (long long)need);
-    return SAPCU_OK;
-}
-
 extern "C" {
 
 int64_t sapcu_ray_mesh_workspace_bytes(int64_t nv, int64_t nf, int64_t nq) {
-    if (!ray_sizes_ok(nv, nf, nq)) return -1;
-    return (int64_t)ray_ws_layout(nullptr, nf, nq).bytes;
+    return mesh_sizes_ok(nv, nf, nq) ? (int64_t)ray_ws_layout(nullptr, nf, nq).bytes : -1;
 }
 
 int sapcu_ray_mesh_f64(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, const double* origins, const double* dirs,
                        const double* t_max, int64_t nq, double cell_size, double* t_out, int64_t* face_out, double* hit_out,
                        void* workspace, int64_t workspace_bytes, int64_t* info_host, void* stream) {
-    const int64_t need = ray_sizes_ok(nv, nf, nq) ? (int64_t)ray_ws_layout(nullptr, nf, nq).bytes : 0;
-    const int rc = ray_check("ray_mesh", vertices, nv, faces, nf, origins && dirs && t_out, nq, cell_size, workspace, workspace_bytes, need);
+    const int rc = mesh_args_check("ray_mesh", "n", vertices, nv, faces, nf, origins && dirs && t_out, nq, cell_size, workspace, workspace_bytes,
+                                   sapcu_ray_mesh_workspace_bytes(nv, nf, nq));
     if (rc != SAPCU_OK) return rc;
     return launch_ray_mesh(vertices, nv, faces, nf, origins, dirs, t_max, nq, cell_size, RAY_OVERSIZE_MULT, RAY_CELL_POP, RAY_PIECE_CELLS,
                            RAY_ROUTE_AUTO, t_out, face_out, hit_out, workspace, info_host, (hipStream_t)stream);
 }
 
 int64_t sapcu_ray_fd_samples_workspace_bytes(int64_t nv, int64_t nf, int64_t n) {
-    if (!ray_sizes_ok(nv, nf, n)) return -1;
-    return (int64_t)fd_ray_ws_layout(nullptr, nf, n).bytes;
+    return mesh_sizes_ok(nv, nf, n) ? (int64_t)fd_ray_ws_layout(nullptr, nf, n).bytes : -1;
 }
 
 int sapcu_ray_fd_samples_f64(const double* vertices, int64_t nv, const int32_t* faces, int64_t nf, const double* surf, const int64_t* sface,
                              const double* g, const double* w, int64_t n, double cell_size, double* points_out, double* normals_out,
                              double* lens_out, uint8_t* keep_out, void* workspace, int64_t workspace_bytes, int64_t* info_host,
                              void* stream) {
-    const int64_t need = ray_sizes_ok(nv, nf, n) ? (int64_t)fd_ray_ws_layout(nullptr, nf, n).bytes : 0;
-    const int rc = ray_check("ray_fd_samples", vertices, nv, faces, nf, surf && sface && g && w && points_out && normals_out && lens_out && keep_out,
-                             n, cell_size, workspace, workspace_bytes, need);
+    const int rc = mesh_args_check("ray_fd_samples", "n", vertices, nv, faces, nf,
+                                   surf && sface && g && w && points_out && normals_out && lens_out && keep_out, n, cell_size, workspace,
+                                   workspace_bytes, sapcu_ray_fd_samples_workspace_bytes(nv, nf, n));
     if (rc != SAPCU_OK) return rc;
     if (info_host) info_host[0] = info_host[1] = info_host[2] = info_host[3] = info_host[4] = info_host[5] = 0;
     if (n == 0) return SAPCU_OK;
@@ -613,8 +552,8 @@ int sapcu_internal_ray_mesh_tuned(const double* vertices, int64_t nv, const int3
                                   const double* dirs, const double* t_max, int64_t nq, double cell_size, double oversize_mult, int cell_pop,
                                   double piece_cells, int route, double* t_out, int64_t* face_out, double* hit_out, void* workspace,
                                   int64_t workspace_bytes, int64_t* info_host, void* stream) {
-    const int64_t need = ray_sizes_ok(nv, nf, nq) ? (int64_t)ray_ws_layout(nullptr, nf, nq).bytes : 0;
-    const int rc = ray_check("ray_mesh_tuned", vertices, nv, faces, nf, origins && dirs && t_out, nq, cell_size, workspace, workspace_bytes, need);
+    const int rc = mesh_args_check("ray_mesh_tuned", "n", vertices, nv, faces, nf, origins && dirs && t_out, nq, cell_size, workspace,
+                                   workspace_bytes, sapcu_ray_mesh_workspace_bytes(nv, nf, nq));
     if (rc != SAPCU_OK) return rc;
     SAPCU_CHECK_ARG(oversize_mult > 0.0 && oversize_mult < 1e300 && cell_pop >= 1 && cell_pop <= 4096 && piece_cells >= 0.125 &&
                         piece_cells <= 1024.0 && route >= 0 && route <= 2,

@@ -4,7 +4,8 @@
     python tests/golden/record_workspace_sizes.py
 
 Public ABI only, so the same file runs on any earlier commit: the recorded numbers are the sizers' values at the commit BEFORE sizer
-and carving became one layout function per workspace, and they are not to be re-recorded because a layout changed by accident.  Two
+and carving became one layout function per workspace (the four sizers of the grid searches: at the commit before their query
+tables became one layout, csrc/knn_grid.h), and they are not to be re-recorded because a layout changed by accident.  Two
 sections:
 
   "sizers"   the handle-free *_workspace_bytes functions over a grid of small and awkward arguments (the library loads without a GPU)
@@ -55,6 +56,12 @@ def record_sizers(lib):
     out["sapcu_knn_grid_workspace_bytes"] = [[n, int(lib.sapcu_knn_grid_workspace_bytes(n))] for n in NS]
     out["sapcu_dense_seeds_workspace_bytes"] = [[n, v, int(lib.sapcu_dense_seeds_workspace_bytes(n, v))] for n in NS for v in NS]
     out["sapcu_fps_workspace_bytes"] = [[n, int(lib.sapcu_fps_workspace_bytes(n))] for n in NS]
+    # the searches on the cell grid: every count over NS, and one refused argument each (-1)
+    out["sapcu_nn_cross_workspace_bytes"] = [[n, q, int(lib.sapcu_nn_cross_workspace_bytes(n, q))] for n in NS for q in NS] + \
+        [[0, 1, int(lib.sapcu_nn_cross_workspace_bytes(0, 1))]]
+    for name in ("sapcu_point_mesh_workspace_bytes", "sapcu_ray_mesh_workspace_bytes", "sapcu_ray_fd_samples_workspace_bytes"):
+        fn = getattr(lib, name)
+        out[name] = [[v, f, q, int(fn(v, f, q))] for v in NS for f in NS for q in NS] + [[1, 0, 1, int(fn(1, 0, 1))]]
     return out
 
 
