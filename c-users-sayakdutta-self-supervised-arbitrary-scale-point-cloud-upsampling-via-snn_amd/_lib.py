@@ -28,7 +28,10 @@ class SapcuError(RuntimeError):
     """A C entry point returned a non-zero status: args = (code, text)."""
 
 
-_SIGNATURES = {
+# header under include/ -> {entry point: (restype, argtypes)}, in the order the headers were added; None: the test hooks in no header.
+# load() binds every table, and tests/abi_tables.py holds each against its header: a new header is one entry here
+TABLES = {}
+TABLES["sapcu.h"] = {
     "sapcu_abi_version": (c_int, []),
     "sapcu_last_error": (c_char_p, []),
     "sapcu_knn_gather_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -86,18 +89,18 @@ _SIGNATURES = {
                                         c_int64, c_void_p]),
 }
 
-EXPORTS = tuple(_SIGNATURES)
+EXPORTS = tuple(TABLES["sapcu.h"])
 
 # include/sapcu_seeds.h: the device seed flood (additions to the same library; EXPORTS stays "what sapcu.h declares")
-_SEEDS_SIGNATURES = {
+TABLES["sapcu_seeds.h"] = {
     "sapcu_dense_seeds_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "sapcu_dense_seeds_f64": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64),
                               c_void_p, c_int64, c_void_p]),
 }
-SEEDS_EXPORTS = tuple(_SEEDS_SIGNATURES)
+SEEDS_EXPORTS = tuple(TABLES["sapcu_seeds.h"])
 
 # include/sapcu_fd_train.h: the training ops of fd (additions to the same library, a third table like SEEDS_EXPORTS)
-_FD_TRAIN_SIGNATURES = {
+TABLES["sapcu_fd_train.h"] = {
     "sapcu_fd_neuron_step_forward": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 6 + [c_void_p] * 3 + [c_void_p] + [c_void_p] * 5 +
                                      [c_void_p]),
     "sapcu_fd_neuron_step_workspace_bytes": (c_int64, [c_int64, c_int]),
@@ -110,10 +113,10 @@ _FD_TRAIN_SIGNATURES = {
     "sapcu_fd_bn_lrelu_max_forward": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p, c_void_p]),
     "sapcu_fd_bn_lrelu_max_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p]),
 }
-FD_TRAIN_EXPORTS = tuple(_FD_TRAIN_SIGNATURES)
+FD_TRAIN_EXPORTS = tuple(TABLES["sapcu_fd_train.h"])
 
 # include/sapcu_fd_edgeconv.h: the factored EdgeConv training op of fd's blocks 1-3 (a fourth table)
-_FD_EDGECONV_SIGNATURES = {
+TABLES["sapcu_fd_edgeconv.h"] = {
     "sapcu_fd_edgeconv_stats_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int]),
     "sapcu_fd_edgeconv_stats": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float] + [c_void_p] * 4 + [c_void_p, c_int64, c_void_p]),
     "sapcu_fd_edgeconv_max_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p, c_void_p]),
@@ -121,50 +124,50 @@ _FD_EDGECONV_SIGNATURES = {
     "sapcu_fd_edgeconv_backward": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int] + [c_void_p] * 4 + [c_void_p] * 4 +
                                    [c_void_p, c_int64, c_void_p]),
 }
-FD_EDGECONV_EXPORTS = tuple(_FD_EDGECONV_SIGNATURES)
+FD_EDGECONV_EXPORTS = tuple(TABLES["sapcu_fd_edgeconv.h"])
 
 # include/sapcu_train_step.h: the device-side skip of a graphed training step (a fifth table); flag, dst, src and nbytes are DEVICE arrays
-_TRAIN_STEP_SIGNATURES = {
+TABLES["sapcu_train_step.h"] = {
     "sapcu_multi_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
-TRAIN_STEP_EXPORTS = tuple(_TRAIN_STEP_SIGNATURES)
+TRAIN_STEP_EXPORTS = tuple(TABLES["sapcu_train_step.h"])
 
 # include/sapcu_metrics.h: the nearest neighbour of every query in another cloud on the device cell grid (a sixth table)
-_METRICS_SIGNATURES = {
+TABLES["sapcu_metrics.h"] = {
     "sapcu_nn_cross_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "sapcu_nn_cross_grid_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_int64,
                                         POINTER(c_int64), c_void_p]),
 }
-METRICS_EXPORTS = tuple(_METRICS_SIGNATURES)
+METRICS_EXPORTS = tuple(TABLES["sapcu_metrics.h"])
 
 # include/sapcu_data.h: fd's and fn's training samples from raw cloud pairs (a seventh table)
-_DATA_SIGNATURES = {
+TABLES["sapcu_data.h"] = {
     "sapcu_train_patches_workspace_bytes": (c_int64, [c_int64]),
     "sapcu_train_patches_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_void_p, c_int64, c_void_p]),
 }
-DATA_EXPORTS = tuple(_DATA_SIGNATURES)
+DATA_EXPORTS = tuple(TABLES["sapcu_data.h"])
 
 # include/sapcu_mesh.h: the distance from every query to a triangle mesh, nearest face and closest point (an eighth table)
-_MESH_SIGNATURES = {
+TABLES["sapcu_mesh.h"] = {
     "sapcu_point_mesh_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "sapcu_point_mesh_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_int64, POINTER(c_int64), c_void_p]),
 }
-MESH_EXPORTS = tuple(_MESH_SIGNATURES)
+MESH_EXPORTS = tuple(TABLES["sapcu_mesh.h"])
 
 # include/sapcu_surface.h: area-weighted sampling of triangle meshes, fn's training clouds from .off files (a ninth table)
-_SURFACE_SIGNATURES = {
+TABLES["sapcu_surface.h"] = {
     "sapcu_surface_tables_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "sapcu_surface_tables_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 4 +
                                  [c_void_p, c_int64, c_void_p]),
     "sapcu_surface_sample_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                          c_void_p, c_int64, c_int] + [c_void_p] * 3 + [c_void_p] * 3 + [c_void_p]),
 }
-SURFACE_EXPORTS = tuple(_SURFACE_SIGNATURES)
+SURFACE_EXPORTS = tuple(TABLES["sapcu_surface.h"])
 
 # include/sapcu_sinkhorn.h: entropic optimal transport between two clouds without the cost matrix (a tenth table)
-_SINKHORN_SIGNATURES = {
+TABLES["sapcu_sinkhorn.h"] = {
     "sapcu_sinkhorn_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "sapcu_softmin_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_double, c_void_p, c_void_p, c_int64, c_void_p]),
     "sapcu_sinkhorn_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(c_double), c_int64, c_double, c_int64, c_void_p,
@@ -172,10 +175,10 @@ _SINKHORN_SIGNATURES = {
     "sapcu_plan_stats_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_void_p]),
 }
-SINKHORN_EXPORTS = tuple(_SINKHORN_SIGNATURES)
+SINKHORN_EXPORTS = tuple(TABLES["sapcu_sinkhorn.h"])
 
 # include/sapcu_ray.h: where every ray first meets a triangle mesh, and the fused step of fd's ray sampler (an eleventh table)
-_RAY_SIGNATURES = {
+TABLES["sapcu_ray.h"] = {
     "sapcu_ray_mesh_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "sapcu_ray_mesh_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
@@ -183,18 +186,18 @@ _RAY_SIGNATURES = {
     "sapcu_ray_fd_samples_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double] +
                                  [c_void_p] * 4 + [c_void_p, c_int64, POINTER(c_int64), c_void_p]),
 }
-RAY_EXPORTS = tuple(_RAY_SIGNATURES)
+RAY_EXPORTS = tuple(TABLES["sapcu_ray.h"])
 
 # include/sapcu_normals.h: PCA normals from a neighbour table and the angle between two tables of normals (a twelfth table);
 # viewpoint_host is a HOST double[3] or None
-_NORMALS_SIGNATURES = {
+TABLES["sapcu_normals.h"] = {
     "sapcu_pca_normals_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
     "sapcu_normal_angles_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
 }
-NORMALS_EXPORTS = tuple(_NORMALS_SIGNATURES)
+NORMALS_EXPORTS = tuple(TABLES["sapcu_normals.h"])
 
 # test hooks in no header (host pointers, no device work): the f64 fold of an fn block's out_proj and fc2 that sapcu_model_create runs
-_INTERNAL_SIGNATURES = {
+TABLES[None] = _INTERNAL_SIGNATURES = {
     "sapcu_internal_fold_affine_host": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     # sapcu_point_mesh_f64 with the oversize cap (in cell edges) and the cell population given, or forced to the brute-force route: profiles/mesh_dist.py, tests/test_gpu_mesh.py
     "sapcu_internal_point_mesh_tuned": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_void_p,
@@ -227,11 +230,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_SEEDS_SIGNATURES.items()) + list(_FD_TRAIN_SIGNATURES.items()) + \
-            list(_FD_EDGECONV_SIGNATURES.items()) + list(_TRAIN_STEP_SIGNATURES.items()) + list(_METRICS_SIGNATURES.items()) + \
-            list(_DATA_SIGNATURES.items()) + list(_MESH_SIGNATURES.items()) + list(_SURFACE_SIGNATURES.items()) + \
-            list(_SINKHORN_SIGNATURES.items()) + list(_RAY_SIGNATURES.items()) + list(_NORMALS_SIGNATURES.items()) + \
-            list(_INTERNAL_SIGNATURES.items()):
+    for name, (res, args) in ((name, sig) for table in TABLES.values() for name, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -259,3 +258,22 @@ def ptr(t):
 def current_stream():
     import torch
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def workspace(sizer, sizes, dev, refusal):
+    """(workspace, nbytes) for one call: what the sizer ``sizer`` returns for the integer arguments ``sizes``, as a zeroed uint8
+    tensor on ``dev``.  A negative size is the sizer's refusal: ``ValueError(refusal)``."""
+    import torch
+    nbytes = int(getattr(load(), sizer)(*sizes))
+    if nbytes < 0:
+        raise ValueError(refusal)
+    return torch.zeros((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
+def call(name, dev, *args):
+    """Run the entry point ``name`` on the current stream of ``dev``: a tensor argument goes in as its device pointer, None, numbers
+    and ctypes values as they are, the stream is appended as the last argument, and a non-zero status raises ``SapcuError``."""
+    import torch
+    fn, tensor = getattr(load(), name), torch.Tensor
+    with torch.cuda.device(dev):
+        check(fn(*[c_void_p(a.data_ptr()) if isinstance(a, tensor) else a for a in args], current_stream()))

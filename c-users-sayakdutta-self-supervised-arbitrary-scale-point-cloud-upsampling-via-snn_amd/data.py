@@ -15,13 +15,14 @@ and cast afresh on the device (``ray.sample_fd_rays``).
 
 No CPU path: the HIP library and a device are required.
 """
+import functools
 import math
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, mesh as mesh_mod, ray as ray_mod, surface
+from . import _inputs, _lib, mesh as mesh_mod, ray as ray_mod, surface
 
 MAX_N, MAX_G, MAX_K = 4096, 65536, 128
 
@@ -46,26 +47,8 @@ def build_patches(clouds, sample_idx, k, dense=None, normals=None, rotation=None
     int32 [b,pc,k], ``cloud`` [b,n,3], with dense ``dense`` [b,g,3] and ``len`` [b,n], with normals ``normals`` [b,n,3] and
     ``patch_normals`` [b,pc,3].  Index VALUES are checked here (one synchronisation; ``validate=False`` skips it — the kernels
     then leave the rows of a bad index unwritten, NaN): ValueError.  CPU tensors: RuntimeError; bad shapes: ValueError."""
-    def dev_tensor(t, name, dtype, shape):
-        if t is None:
-            return None
-        if not torch.is_tensor(t):
-            raise ValueError("%s: expected a device tensor" % name)
-        if not t.is_cuda:
-            raise RuntimeError("%s: a CPU tensor (there is no CPU path)" % name)
-        if t.dim() != len(shape) or any(w is not None and s != w for s, w in zip(t.shape, shape)):
-            raise ValueError("%s: expected shape %s, got %s" % (name, list(shape), list(t.shape)))
-        if t.device != clouds.device:
-            raise ValueError("%s: on %s, the clouds are on %s" % (name, t.device, clouds.device))
-        if dtype.is_floating_point != t.dtype.is_floating_point:
-            raise ValueError("%s: expected %s, got %s" % (name, dtype, t.dtype))
-        return t.to(dtype).contiguous()
-
-    if not torch.is_tensor(clouds):
-        raise ValueError("clouds: expected a device tensor")
-    if not clouds.is_cuda:
-        raise RuntimeError("clouds: a CPU tensor (there is no CPU path)")
-    clouds = dev_tensor(clouds, "clouds", torch.float32, (None, None, 3))
+    clouds = _inputs.device_tensor(getattr(clouds, "device", None), "the clouds", clouds, "clouds", torch.float32, (None, None, 3))
+    dev_tensor = functools.partial(_inputs.device_tensor, clouds.device, "the clouds", optional=True)
     S, n = clouds.shape[0], clouds.shape[1]
     if S < 1 or not 1 <= n <= MAX_N:
         raise ValueError("clouds: need at least one sample and 1 <= n <= %d points, got %s" % (MAX_N, list(clouds.shape)))
@@ -106,17 +89,11 @@ def build_patches(clouds, sample_idx, k, dense=None, normals=None, rotation=None
         out["patch_normals"] = torch.full((b, pc, 3), nan, dtype=torch.float32, device=dev)
     if b == 0:
         return out
-    lib = _lib.load()
-    nbytes = int(lib.sapcu_train_patches_workspace_bytes(b))
-    if nbytes < 0:
-        raise ValueError("sample_idx: a batch of %d entries is outside the range of the call" % b)
-    ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(lib.sapcu_train_patches_f32(
-            p(clouds), S, n, p(dense), g, p(normals), p(sample_idx), b, p(rotation), p(scale), p(jitter), p(centres), pc, k,
-            p(out["patches"]), p(out["idx"]), p(out["cloud"]), p(out.get("dense")), p(out.get("len")), p(out.get("normals")),
-            p(out.get("patch_normals")), p(ws), nbytes, _lib.current_stream()))
+    ws, nbytes = _lib.workspace("sapcu_train_patches_workspace_bytes", (b,), dev,
+                                "sample_idx: a batch of %d entries is outside the range of the call" % b)
+    _lib.call("sapcu_train_patches_f32", dev, clouds, S, n, dense, g, normals, sample_idx, b, rotation, scale, jitter, centres, pc, k,
+              out["patches"], out["idx"], out["cloud"], out.get("dense"), out.get("len"), out.get("normals"), out.get("patch_normals"),
+              ws, nbytes)
     return out
 
 

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 from . import metrics
 
 
@@ -29,8 +29,7 @@ def point_to_mesh(points, vertices, faces, cell_size=0.0, info=None):
     A point that no face gives a distance for (a NaN point, every face skipped) gets NaN, -1, NaN.  ``cell_size`` 0 = automatic
     (any value gives the same result, bit for bit).  ``info``, a list, receives [route (0 brute force, 1 grid), gx, gy, gz, faces
     on the oversize list, faces skipped].  Synchronises the current stream once."""
-    points, vertices, faces = _on_device(points, vertices, faces)
-    lib = _lib.load()
+    points, vertices, faces = on_device(points, vertices, faces)
     nq, nv, nf = points.shape[0], vertices.shape[0], faces.shape[0]
     dev = vertices.device
     dist = torch.full((nq,), float("nan"), dtype=torch.float64, device=dev)
@@ -38,14 +37,9 @@ def point_to_mesh(points, vertices, faces, cell_size=0.0, info=None):
     closest = torch.full((nq, 3), float("nan"), dtype=torch.float64, device=dev)
     out = (ctypes.c_int64 * 6)()
     if nq:
-        nbytes = int(lib.sapcu_point_mesh_workspace_bytes(nv, nf, nq))
-        if nbytes < 0:
-            raise ValueError("point_to_mesh: %d vertices, %d faces and %d points are outside the search's range" % (nv, nf, nq))
-        ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sapcu_point_mesh_f64(_lib.ptr(vertices), nv, _lib.ptr(faces), nf, _lib.ptr(points), nq, float(cell_size),
-                                                _lib.ptr(dist), _lib.ptr(face), _lib.ptr(closest), _lib.ptr(ws), nbytes, out,
-                                                _lib.current_stream()))
+        ws, nbytes = _lib.workspace("sapcu_point_mesh_workspace_bytes", (nv, nf, nq), dev,
+                                    "point_to_mesh: %d vertices, %d faces and %d points are outside the search's range" % (nv, nf, nq))
+        _lib.call("sapcu_point_mesh_f64", dev, vertices, nv, faces, nf, points, nq, float(cell_size), dist, face, closest, ws, nbytes, out)
     if info is not None:
         info[:] = list(out)
     return dist, face, closest
@@ -138,8 +132,8 @@ def evaluate_mesh_file(pred_path, mesh_path, device="cuda"):
                         torch.from_numpy(faces).to(dev))
 
 
-# ------------------------------------------------------------------------------------------------------------ internals
-def _checked_faces(faces):
+def checked_faces(faces):
+    """The faces of a mesh after their host checks: shape, integer dtype, placement, at least one face."""
     if torch.is_tensor(faces):
         shape, on_host = tuple(faces.shape), not faces.is_cuda
         integer = not (faces.dtype.is_floating_point or faces.dtype.is_complex or faces.dtype == torch.bool)
@@ -157,46 +151,35 @@ def _checked_faces(faces):
     return faces
 
 
-def _on_device(points, vertices, faces):
-    """points and vertices as contiguous f64 [n,3], faces as contiguous int32 [nf,3] with every index in [0, nv), on one device."""
-    points, vertices = metrics._checked(points, "points"), metrics._checked(vertices, "vertices")
-    faces = _checked_faces(faces)
-    nv = vertices.shape[0]
+def on_device(points, vertices, faces, name="points", min_rows=0, finite=False):
+    """points (called ``name`` in messages) and vertices as contiguous f64 [n,3], faces as contiguous int32 [nf,3] with every index
+    in [0, nv), on one device.  ``min_rows`` and ``finite`` are the points' and, ``finite``, the vertices' checks of
+    ``_inputs.on_device``; the range check of the faces (one read-back) comes before the device tensors' values are tested."""
+    _inputs.checked(points, name), _inputs.checked(vertices, "vertices")      # shape, dtype, placement of both before the rest
+    xs = [_inputs.checked(points, name, min_rows, finite), _inputs.checked(vertices, "vertices", 0, finite)]
+    faces = checked_faces(faces)
+    nv = xs[1].shape[0]
     if nv < 1:
         raise ValueError("vertices: an empty mesh")
-    dev = next((t.device for t in (points, vertices, faces) if torch.is_tensor(t)), None)
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    out = []
-    for x in (points, vertices):
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
-        out.append(x.to(device=dev, dtype=torch.float64).contiguous())
+    out = _inputs.upload(xs, others=(faces,))
     if not torch.is_tensor(faces):
         if faces.dtype.kind == "u":
             if int(faces.max()) >= nv:
                 raise ValueError("faces: an index outside [0, %d)" % nv)
         faces = torch.from_numpy(np.ascontiguousarray(faces).astype(np.int64))
-    faces = faces.to(device=dev)
+    faces = faces.to(device=out[0].device)
     lo, hi = int(faces.min()), int(faces.max())
     if lo < 0 or hi >= nv:
         raise ValueError("faces: an index outside [0, %d) (smallest %d, largest %d)" % (nv, lo, hi))
-    out.append(faces.to(torch.int32).contiguous())
-    return out
+    if finite:
+        _inputs.finite_on_device(xs, out, (name, "vertices"))
+    return out + [faces.to(torch.int32).contiguous()]
 
 
+# ------------------------------------------------------------------------------------------------------------ internals
 def _distances(pred, vertices, faces):
     """(dist f64 [n_pre] on the device, faces, skipped faces); the input checks of mesh_metrics."""
-    pred, vertices = metrics._checked(pred, "pred"), metrics._checked(vertices, "vertices")
-    if pred.shape[0] < 1:
-        raise ValueError("pred: an empty cloud")
-    for x, name in ((pred, "pred"), (vertices, "vertices")):
-        if not torch.is_tensor(x) and not np.isfinite(x).all():
-            raise ValueError("%s contains NaN or infinity" % name)
-    pred, vertices, faces = _on_device(pred, vertices, faces)
-    for x, name in ((pred, "pred"), (vertices, "vertices")):
-        if not bool(torch.isfinite(x).all()):
-            raise ValueError("%s contains NaN or infinity" % name)
+    pred, vertices, faces = on_device(pred, vertices, faces, "pred", min_rows=1, finite=True)
     info = []
     d = point_to_mesh(pred, vertices, faces, info=info)[0]
     nf = int(faces.shape[0])
@@ -205,11 +188,7 @@ def _distances(pred, vertices, faces):
     return d, nf, int(info[5])
 
 
-def _figures(d, n_faces, n_skipped, bufsize=None):
-    n = d.numel()
-    mean = np.float64(metrics._np_sum(d, bufsize)) / n
-    x = d - float(mean)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        std = np.sqrt(np.float64(metrics._np_sum(x * x, bufsize)) / np.float64(n - 1))
-    return {"p2f_mean": mean, "p2f_std": std, "p2f_min": np.float64(d.min().item()), "p2f_max": np.float64(d.max().item()),
-            "n_pre": int(n), "n_faces": int(n_faces), "n_skipped": int(n_skipped)}
+def _figures(d, n_faces, n_skipped):
+    mean, std, lo, hi = metrics.moments(d, 1)
+    return {"p2f_mean": mean, "p2f_std": std, "p2f_min": lo, "p2f_max": hi,
+            "n_pre": int(d.numel()), "n_faces": int(n_faces), "n_skipped": int(n_skipped)}

@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 from . import generation
 
 THRESHOLDS = (1e-2, 2e-2)
@@ -29,21 +29,16 @@ def nearest(queries, cloud, cell_size=0.0, info=None):
     """Exact nearest neighbour of every query f64 [nq,3] in ``cloud`` f64 [n,3], both on the device: (dist f64 [nq], idx int64 [nq]),
     bit for bit ``knn_gather(cloud, queries, 1, want_dist=True)``.  ``cell_size`` 0 = automatic (any value gives the same result).
     ``info``, a list, receives [1 if the grid ran else 0 (brute force), gx, gy, gz].  Synchronises the current stream once."""
-    queries, cloud = _pair_on_device(queries, cloud, ("queries", "cloud"))
-    lib = _lib.load()
+    queries, cloud = _inputs.on_device(((queries, "queries"), (cloud, "cloud")), min_rows=(0, 1))
     n, nq = cloud.shape[0], queries.shape[0]
     dev = cloud.device
     dist = torch.full((nq,), float("nan"), dtype=torch.float64, device=dev)
     idx = torch.full((nq,), -1, dtype=torch.int64, device=dev)
     out = (ctypes.c_int64 * 4)()
     if nq:
-        nbytes = int(lib.sapcu_nn_cross_workspace_bytes(n, nq))
-        if nbytes < 0:
-            raise ValueError("nearest: a cloud of %d points and %d queries are outside the search's range" % (n, nq))
-        ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sapcu_nn_cross_grid_f64(_lib.ptr(cloud), n, _lib.ptr(queries), nq, float(cell_size), _lib.ptr(dist),
-                                                   _lib.ptr(idx), _lib.ptr(ws), nbytes, out, _lib.current_stream()))
+        ws, nbytes = _lib.workspace("sapcu_nn_cross_workspace_bytes", (n, nq), dev,
+                                    "nearest: a cloud of %d points and %d queries are outside the search's range" % (n, nq))
+        _lib.call("sapcu_nn_cross_grid_f64", dev, cloud, n, queries, nq, float(cell_size), dist, idx, ws, nbytes, out)
     if info is not None:
         info[:] = list(out)
     return dist, idx
@@ -68,74 +63,48 @@ def dataset_metrics(pairs, thresholds=THRESHOLDS):
     return _figures(torch.cat([a for a, _ in both]), torch.cat([b for _, b in both]), thresholds)
 
 
-# ------------------------------------------------------------------------------------------------------------ internals
-def _checked(x, name):
-    """Shape, emptiness and placement of one input, before anything touches the device."""
-    if torch.is_tensor(x):
-        shape, on_host, floating = tuple(x.shape), not x.is_cuda, x.dtype.is_floating_point
-    else:
-        x = np.asarray(x)
-        shape, on_host, floating = x.shape, False, x.dtype.kind == "f"
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError("%s: expected points [n, 3], got shape %s" % (name, tuple(shape)))
-    if not floating:
-        raise ValueError("%s: expected a floating dtype" % name)
-    if on_host:
-        raise RuntimeError("%s: a CPU tensor (there is no CPU path; pass a device tensor or a numpy array)" % name)
-    return x
-
-
-def _pair_on_device(a, b, names):
-    """Both inputs as contiguous f64 [n,3] tensors on one device (a tensor's own, else the current one)."""
-    a, b = _checked(a, names[0]), _checked(b, names[1])
-    if b.shape[0] < 1:
-        raise ValueError("%s: an empty cloud" % names[1])
-    dev = next((t.device for t in (a, b) if torch.is_tensor(t)), None)
-    if dev is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    out = []
-    for x in (a, b):
-        if not torch.is_tensor(x):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
-        out.append(x.to(device=dev, dtype=torch.float64).contiguous())
-    return out
-
-
-def _pair_distances(pred, gt):
-    """(gt2pre f64 [n_gt], pre2gt f64 [n_pre]) on the device; the input checks of cloud_metrics."""
-    pred, gt = _checked(pred, "pred"), _checked(gt, "gt")
-    for x, name in ((pred, "pred"), (gt, "gt")):
-        if x.shape[0] < 1:
-            raise ValueError("%s: an empty cloud" % name)
-        if not torch.is_tensor(x) and not np.isfinite(x).all():
-            raise ValueError("%s contains NaN or infinity" % name)
-    pred, gt = _pair_on_device(pred, gt, ("pred", "gt"))
-    for x, name in ((pred, "pred"), (gt, "gt")):
-        if not bool(torch.isfinite(x).all()):
-            raise ValueError("%s contains NaN or infinity" % name)
-    return nearest(gt, pred)[0], nearest(pred, gt)[0]
-
-
-def _np_sum(v, bufsize=None):
-    """np.sum of a device f64 vector in numpy's order, as a Python float."""
+def np_sum(v, bufsize=None):
+    """np.sum of a device f64 vector in numpy's order (pairwise within chunks of ``bufsize`` elements, None = ``np.getbufsize()``,
+    the chunk sums added in sequence), as a Python float."""
     _, sums = generation.outlier_stats_device(v.view(-1, 1), bufsize)
     return generation.outlier_global_mean(sums.cpu(), 1)
 
 
-def _direction(d, thresholds, bufsize=None):
-    """np.mean, np.std, max and the rates np.mean(d <= t) of one device distance vector."""
+def moments(d, ddof, bufsize=None):
+    """(mean, std, min, max) of a device f64 vector as ``np.float64``, equal to numpy's: ``np.mean``, numpy's ``_var`` (the
+    deviations and their squares as two f64 operations on the device, the same chunked sum) and ``sqrt`` on the host.  ``ddof`` 0
+    divides by n, as ``np.std``; ``ddof`` 1 by ``np.float64(n - 1)``, the sample deviation, NaN for a single value."""
     n = d.numel()
-    mean = np.float64(_np_sum(d, bufsize)) / n
-    x = d - float(mean)                                           # numpy's _var: the deviations, their squares, the same sum
-    std = np.sqrt(np.float64(_np_sum(x * x, bufsize)) / n)
-    rates = tuple(np.float64(int((d <= float(t)).sum())) / n for t in thresholds)
-    return mean, std, np.float64(d.max().item()), rates
+    mean = np.float64(np_sum(d, bufsize)) / n
+    x = d - float(mean)
+    squares = np.float64(np_sum(x * x, bufsize))
+    if ddof == 0:
+        std = np.sqrt(squares / n)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            std = np.sqrt(squares / np.float64(n - ddof))
+    lo, hi = torch.stack(torch.aminmax(d)).tolist()
+    return mean, std, np.float64(lo), np.float64(hi)
 
 
-def _figures(gt2pre, pre2gt, thresholds, bufsize=None):
+# ------------------------------------------------------------------------------------------------------------ internals
+def _pair_distances(pred, gt):
+    """(gt2pre f64 [n_gt], pre2gt f64 [n_pre]) on the device; the input checks of cloud_metrics."""
+    pred, gt = _inputs.on_device(((pred, "pred"), (gt, "gt")), min_rows=1, finite=True)
+    return nearest(gt, pred)[0], nearest(pred, gt)[0]
+
+
+def _direction(d, thresholds):
+    """np.mean, np.std, max and the rates np.mean(d <= t) of one device distance vector."""
+    mean, std, _, top = moments(d, 0)
+    rates = tuple(np.float64(int((d <= float(t)).sum())) / d.numel() for t in thresholds)
+    return mean, std, top, rates
+
+
+def _figures(gt2pre, pre2gt, thresholds):
     thresholds = tuple(thresholds)
-    gm, gs, gmax, recall = _direction(gt2pre, thresholds, bufsize)
-    pm, ps, pmax, precision = _direction(pre2gt, thresholds, bufsize)
+    gm, gs, gmax, recall = _direction(gt2pre, thresholds)
+    pm, ps, pmax, precision = _direction(pre2gt, thresholds)
     fscore = tuple(np.float64(0.0) if r == 0 or p == 0 else 2 / (1 / r + 1 / p) for r, p in zip(recall, precision))
     return {"gt2pre_mean": gm, "gt2pre_std": gs, "gt2pre_max": gmax, "recall": recall,
             "pre2gt_mean": pm, "pre2gt_std": ps, "pre2gt_max": pmax, "precision": precision,

@@ -13,7 +13,7 @@ A PCA normal has no orientation.  ``pca_normals`` fixes the sign by a rule inste
 viewpoint the component of largest magnitude is positive, with one the normal points to the viewpoint's side.
 
 Every float of ``normal_metrics`` equals numpy's on the device's own angle vector (``==``): mean and rms go through numpy's chunked
-pairwise sum (``metrics._np_sum``), the median is the average of the two middle values of the sorted vector, the rates are integer
+pairwise sum (``metrics.np_sum``), the median is the average of the two middle values of the sorted vector, the rates are integer
 counts.
 
 No CPU path: the HIP library and a device are required.
@@ -23,7 +23,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 from . import generation
 from . import metrics
 
@@ -48,7 +48,7 @@ def pca_normals(points, k=16, viewpoint=None, chunk_rows=1 << 20, return_evals=F
     magnitude positive.  ``return_evals``: additionally the eigenvalues f64 [n,3], ascending.  The rows are processed ``chunk_rows``
     at a time (the neighbour table of a chunk is chunk_rows x k x 16 bytes); the result does not depend on it.  Raises ``ValueError``
     for n < 3, k < 3, min(k, n) > 64 or a non-finite coordinate."""
-    points = metrics._checked(points, "points")
+    points = _inputs.checked(points, "points")
     n = int(points.shape[0])
     k = int(k)
     if n < 3:
@@ -62,11 +62,7 @@ def pca_normals(points, k=16, viewpoint=None, chunk_rows=1 << 20, return_evals=F
     if chunk_rows < 1:
         raise ValueError("pca_normals: chunk_rows = %d" % chunk_rows)
     view = _viewpoint(viewpoint)
-    if not torch.is_tensor(points) and not np.isfinite(points).all():
-        raise ValueError("points contains NaN or infinity")
-    pts = _cloud_on_device(points, "points")
-    if not bool(torch.isfinite(pts).all()):
-        raise ValueError("points contains NaN or infinity")
+    pts = _inputs.on_device(((points, "points"),), finite=True)[0]
     normals = torch.full((n, 3), float("nan"), dtype=torch.float64, device=pts.device)
     evals = torch.full((n, 3), float("nan"), dtype=torch.float64, device=pts.device) if return_evals else None
     for r0 in range(0, n, chunk_rows):
@@ -81,7 +77,7 @@ def normal_angles(a, b, oriented=False, clamp_eps=0.0, return_cos=False):
     dtype, any length): ``angular_error_deg`` of the reference's script (unoriented: 0 .. 90) or, with ``oriented=True,
     clamp_eps=1e-6``, the angle of fn's trainer (0 .. 180, the cosine clamped to +-(1 - 1e-6)).  A zero normal gives 90 degrees, a NaN
     stays a NaN.  ``return_cos``: additionally the clamped cosine."""
-    a, b = _pair(a, b, ("a", "b"))
+    a, b = _inputs.on_device(((a, "a"), (b, "b")))
     if a.shape[0] != b.shape[0]:
         raise ValueError("normal_angles: %d and %d rows" % (a.shape[0], b.shape[0]))
     clamp_eps = float(clamp_eps)
@@ -91,10 +87,7 @@ def normal_angles(a, b, oriented=False, clamp_eps=0.0, return_cos=False):
     deg = torch.full((rows,), float("nan"), dtype=torch.float64, device=a.device)
     cos = torch.full((rows,), float("nan"), dtype=torch.float64, device=a.device) if return_cos else None
     if rows:
-        lib = _lib.load()
-        with torch.cuda.device(a.device):
-            _lib.check(lib.sapcu_normal_angles_f64(_lib.ptr(a), _lib.ptr(b), rows, 1 if oriented else 0, clamp_eps, _lib.ptr(cos),
-                                                   _lib.ptr(deg), _lib.current_stream()))
+        _lib.call("sapcu_normal_angles_f64", a.device, a, b, rows, 1 if oriented else 0, clamp_eps, cos, deg)
     return (deg, cos) if return_cos else deg
 
 
@@ -109,20 +102,17 @@ def normal_metrics(pred_normals, gt_normals, pred_points=None, gt_points=None, o
     here the match is by position.)"""
     if (pred_points is None) != (gt_points is None):
         raise ValueError("normal_metrics: pred_points and gt_points go together")
+    a, b = _inputs.on_device(((pred_normals, "pred_normals"), (gt_normals, "gt_normals")))
     if pred_points is None:
-        a, b = _pair(pred_normals, gt_normals, ("pred_normals", "gt_normals"))
         if a.shape[0] != b.shape[0]:
             raise ValueError("normal_metrics: %d predicted and %d ground-truth normals, and no points to match them by"
                              % (a.shape[0], b.shape[0]))
     else:
-        a, b = _pair(pred_normals, gt_normals, ("pred_normals", "gt_normals"))
-        pp, gp = _pair(pred_points, gt_points, ("pred_points", "gt_points"), device=a.device)
+        pp, gp = _inputs.on_device(((pred_points, "pred_points"), (gt_points, "gt_points")), device=a.device)
         if pp.shape[0] != a.shape[0] or gp.shape[0] != b.shape[0]:
             raise ValueError("normal_metrics: %d / %d predicted points / normals, %d / %d ground-truth points / normals"
                              % (pp.shape[0], a.shape[0], gp.shape[0], b.shape[0]))
-        for x, name in ((pp, "pred_points"), (gp, "gt_points")):
-            if not bool(torch.isfinite(x).all()):
-                raise ValueError("%s contains NaN or infinity" % name)
+        _inputs.finite_on_device((pp, gp), (pp, gp), ("pred_points", "gt_points"))       # after the row counts, so both on the device
         b = b[metrics.nearest(pp, gp)[1]] if pp.shape[0] else b[:0]
     if a.shape[0] < 1:
         raise ValueError("normal_metrics: no normal to score")
@@ -155,23 +145,6 @@ def evaluate_normals_file(pred_npz, gt_npz, device="cuda", **kw):
 
 
 # ------------------------------------------------------------------------------------------------------------ internals
-def _cloud_on_device(x, name, device=None):
-    """One [n,3] input as a contiguous f64 tensor on the device (its own, the given one, else the current one)."""
-    x = metrics._checked(x, name)
-    if torch.is_tensor(x):
-        return x.to(device=device or x.device, dtype=torch.float64).contiguous()
-    dev = device or torch.device("cuda", torch.cuda.current_device())
-    return torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(dev)            # a copy: x may be read-only
-
-
-def _pair(a, b, names, device=None):
-    """Two [n,3] inputs as contiguous f64 tensors on one device: `device`, else the first tensor's, else the current one."""
-    a, b = metrics._checked(a, names[0]), metrics._checked(b, names[1])
-    if device is None:
-        device = next((t.device for t in (a, b) if torch.is_tensor(t)), None)
-    return _cloud_on_device(a, names[0], device), _cloud_on_device(b, names[1], device)
-
-
 def _viewpoint(viewpoint):
     """None, or the viewpoint as a host double[3]."""
     if viewpoint is None:
@@ -203,10 +176,7 @@ def _normals_into(pts, idx, view, want_evals, normals=None, evals=None):
         evals = torch.full((rows, 3), float("nan"), dtype=torch.float64, device=dev)
     assert normals.is_contiguous() and (evals is None or evals.is_contiguous())
     bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.sapcu_pca_normals_f64(_lib.ptr(pts), pts.shape[0], _lib.ptr(idx), rows, k, view, _lib.ptr(normals),
-                                             _lib.ptr(evals) if want_evals else None, _lib.ptr(bad), _lib.current_stream()))
+    _lib.call("sapcu_pca_normals_f64", dev, pts, pts.shape[0], idx, rows, k, view, normals, evals if want_evals else None, bad)
     nbad = int(bad.item())
     if nbad:
         raise ValueError("idx: %d entries outside [0, %d)" % (nbad, pts.shape[0]))
@@ -221,7 +191,7 @@ def _host_figures(n, total, total_sq, mid_lo, mid_hi, counts):
             "rms_deg": np.sqrt(np.float64(total_sq) / n), "pgp": tuple(np.float64(int(c)) / n for c in counts), "count": n}
 
 
-def _figures(deg, thresholds, bufsize=None):
+def _figures(deg, thresholds):
     n = deg.numel()
     if bool(torch.isnan(deg).any()):
         mid_lo = mid_hi = float("nan")                                     # np.median of a vector with a NaN
@@ -229,4 +199,4 @@ def _figures(deg, thresholds, bufsize=None):
         ordered = torch.sort(deg).values
         mid_lo, mid_hi = ordered[(n - 1) // 2].item(), ordered[n // 2].item()
     counts = [int((deg <= float(t)).sum()) for t in thresholds]
-    return _host_figures(n, metrics._np_sum(deg, bufsize), metrics._np_sum(deg * deg, bufsize), mid_lo, mid_hi, counts)
+    return _host_figures(n, metrics.np_sum(deg), metrics.np_sum(deg * deg), mid_lo, mid_hi, counts)

@@ -18,7 +18,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 from . import mesh as mesh_mod
 from . import metrics
 from . import surface
@@ -28,14 +28,12 @@ LEN_MIN, LEN_SPAN = 0.003, 0.027
 
 
 def _rays_on_device(origins, directions, vertices, faces, t_max):
-    origins, vertices, faces = mesh_mod._on_device(origins, vertices, faces)
-    directions = metrics._checked(directions, "directions")
+    origins, vertices, faces = mesh_mod.on_device(origins, vertices, faces)
+    directions = _inputs.checked(directions, "directions")
     if tuple(directions.shape) != tuple(origins.shape):
         raise ValueError("directions: shape %s, the origins have %s" % (tuple(directions.shape), tuple(origins.shape)))
     dev = vertices.device
-    if not torch.is_tensor(directions):
-        directions = torch.from_numpy(np.ascontiguousarray(directions, dtype=np.float64))
-    directions = directions.to(device=dev, dtype=torch.float64).contiguous()
+    directions = _inputs.upload([directions], dev)[0]
     if t_max is not None:
         nq = origins.shape[0]
         if torch.is_tensor(t_max):
@@ -64,7 +62,6 @@ def ray_to_mesh(origins, directions, vertices, faces, t_max=None, cell_size=0.0,
     bit for bit).  ``info``, a list, receives [route (0 brute force, 1 grid), gx, gy, gz, faces on the oversize list, faces
     skipped].  Synchronises the current stream once."""
     origins, directions, vertices, faces, t_max = _rays_on_device(origins, directions, vertices, faces, t_max)
-    lib = _lib.load()
     nq, nv, nf = origins.shape[0], vertices.shape[0], faces.shape[0]
     dev = vertices.device
     t = torch.full((nq,), float("inf"), dtype=torch.float64, device=dev)
@@ -72,14 +69,10 @@ def ray_to_mesh(origins, directions, vertices, faces, t_max=None, cell_size=0.0,
     hit = torch.full((nq, 3), float("nan"), dtype=torch.float64, device=dev)
     out = (ctypes.c_int64 * 6)()
     if nq:
-        nbytes = int(lib.sapcu_ray_mesh_workspace_bytes(nv, nf, nq))
-        if nbytes < 0:
-            raise ValueError("ray_to_mesh: %d vertices, %d faces and %d rays are outside the cast's range" % (nv, nf, nq))
-        ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sapcu_ray_mesh_f64(_lib.ptr(vertices), nv, _lib.ptr(faces), nf, _lib.ptr(origins), _lib.ptr(directions),
-                                              _lib.ptr(t_max), nq, float(cell_size), _lib.ptr(t), _lib.ptr(face), _lib.ptr(hit),
-                                              _lib.ptr(ws), nbytes, out, _lib.current_stream()))
+        ws, nbytes = _lib.workspace("sapcu_ray_mesh_workspace_bytes", (nv, nf, nq), dev,
+                                    "ray_to_mesh: %d vertices, %d faces and %d rays are outside the cast's range" % (nv, nf, nq))
+        _lib.call("sapcu_ray_mesh_f64", dev, vertices, nv, faces, nf, origins, directions, t_max, nq, float(cell_size), t, face, hit, ws,
+                  nbytes, out)
     if info is not None:
         info[:] = list(out)
     return t, face, hit
@@ -122,11 +115,8 @@ def ray_metrics(points, normals, pred_d, vertices, faces, t_max=None, bufsize=No
     n = int(e.numel())
     if n < 1:
         raise ValueError("ray_metrics: no point meets the mesh along its normal")
-    mean = np.float64(metrics._np_sum(e, bufsize)) / n
-    x = e - float(mean)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        std = np.sqrt(np.float64(metrics._np_sum(x * x, bufsize)) / np.float64(n - 1))
-    return {"ray_mean": mean, "ray_std": std, "ray_min": np.float64(e.min().item()), "ray_max": np.float64(e.max().item()), "n": n,
+    mean, std, lo, hi = metrics.moments(e, 1, bufsize)
+    return {"ray_mean": mean, "ray_std": std, "ray_min": lo, "ray_max": hi, "n": n,
             "n_missed": int(n_all - n), "n_faces": int(np.shape(faces)[0]), "n_skipped": int(info[5])}
 
 
@@ -199,16 +189,11 @@ def sample_fd_rays(tables, mesh_idx, u, r1, r2, g, w, allow_open=False, cell_siz
         faces = faces.contiguous()
         g = g.to(device=dev, dtype=torch.float64).contiguous()
         w = w.to(device=dev, dtype=torch.float64).contiguous()
-        lib, p = _lib.load(), _lib.ptr
         nv, nf = vertices.shape[0], faces.shape[0]
-        nbytes = int(lib.sapcu_ray_fd_samples_workspace_bytes(nv, nf, n))
-        if nbytes < 0:
-            raise ValueError("sample_fd_rays: %d vertices, %d faces and %d samples are outside the sampler's range" % (nv, nf, n))
-        ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sapcu_ray_fd_samples_f64(p(vertices), nv, p(faces), nf, p(surf), p(sface), p(g), p(w), n, float(cell_size),
-                                                    p(points), p(normals), p(lens), p(keep), p(ws), nbytes, None,
-                                                    _lib.current_stream()))
+        ws, nbytes = _lib.workspace("sapcu_ray_fd_samples_workspace_bytes", (nv, nf, n), dev,
+                                    "sample_fd_rays: %d vertices, %d faces and %d samples are outside the sampler's range" % (nv, nf, n))
+        _lib.call("sapcu_ray_fd_samples_f64", dev, vertices, nv, faces, nf, surf, sface, g, w, n, float(cell_size), points, normals, lens,
+                  keep, ws, nbytes, None)
     keep = keep.bool()
     return keep, points[keep].float(), normals[keep].float(), lens[keep].float()
 

@@ -14,7 +14,7 @@ package's own; tests/sinkhorn_ref.py states the definition in
 * ``ot`` = <a, f> + <b, g>; ``primal_cost`` = sum_ij P_ij C_ij, the figure that tends to the EMD as blur -> 0; ``marginal_error`` =
   sum_i |sum_j P_ij - a_i| (the column marginals are exact after an iteration); ``divergence`` = ot(a,b) - ot(a,a)/2 - ot(b,b)/2.
 
-Every sum over points is ``metrics._np_sum`` (numpy's order), so the floats equal numpy's on the same device vectors.  The loop
+Every sum over points is ``metrics.np_sum`` (numpy's order), so the floats equal numpy's on the same device vectors.  The loop
 only enqueues launches: nothing is read back inside it.  No CPU path: the HIP library and a device are required.
 """
 import ctypes
@@ -22,7 +22,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 from . import metrics
 
 
@@ -53,21 +53,16 @@ def softmin(x, y, pot_y, p, eps):
     and a device potential pot_y [m]."""
     _check_p(p)
     eps = _positive(eps, "eps")
-    x, y = metrics._pair_on_device(x, y, ("x", "y"))
-    if x.shape[0] < 1:
-        raise ValueError("x: an empty cloud")
+    x, y = _clouds(x, y)
     if not torch.is_tensor(pot_y) or not pot_y.is_cuda:
         raise RuntimeError("pot_y: expected a device tensor")
     if pot_y.shape != (y.shape[0],):
         raise ValueError("pot_y: expected shape (%d,), got %s" % (y.shape[0], tuple(pot_y.shape)))
     pot_y = pot_y.to(dtype=torch.float64).contiguous()
-    lib = _lib.load()
     n, m = x.shape[0], y.shape[0]
     out = torch.full((n,), float("nan"), dtype=torch.float64, device=x.device)
-    ws, nbytes = _workspace(lib, n, m, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sapcu_softmin_f64(_lib.ptr(x), n, _lib.ptr(y), m, _lib.ptr(pot_y), int(p), eps, _lib.ptr(out), _lib.ptr(ws), nbytes,
-                                         _lib.current_stream()))
+    ws, nbytes = _workspace(n, m, x.device)
+    _lib.call("sapcu_softmin_f64", x.device, x, n, y, m, pot_y, int(p), eps, out, ws, nbytes)
     return out
 
 
@@ -76,15 +71,8 @@ def sinkhorn_potentials(x, y=None, p=2, blur=0.05, iters=100, scaling=None, *, d
     returned twice.  ``diameter`` (for ``scaling``) defaults to the diagonal of the bounding box of both clouds, read back before
     the loop starts."""
     _check_settings(p, blur, iters, scaling)
-    x = _cloud(x, "x")
-    y = None if y is None else _cloud(y, "y")
-    if y is not None:
-        x, y = metrics._pair_on_device(x, y, ("x", "y"))
-    else:
-        x = metrics._pair_on_device(x, x, ("x", "x"))[0]
-    _finite_on_device(x, "x")
-    if y is not None:
-        _finite_on_device(y, "y")
+    given = [_inputs.checked(x, "x", 1, True)] + ([] if y is None else [_inputs.checked(y, "y", 1, True)])
+    x, y = (_on_device(given, ("x", "y")) + [None])[:2]
     if scaling is not None and diameter is None:
         diameter = _diameter(x, y)
     return _potentials(x, y, p, blur, iters, eps_schedule(diameter, p, blur, scaling))
@@ -98,12 +86,10 @@ def sinkhorn_metrics(pred, gt, p=2, blur=0.05, iters=100, scaling=None, debias=T
     _check_settings(p, blur, iters, scaling)
     if downsample_gt is not None and (isinstance(downsample_gt, bool) or int(downsample_gt) != downsample_gt or downsample_gt < 1):
         raise ValueError("downsample_gt: expected a positive integer or None")
-    pred, gt = _cloud(pred, "pred"), _cloud(gt, "gt")
+    pred, gt = _inputs.checked(pred, "pred", 1, True), _inputs.checked(gt, "gt", 1, True)
     if downsample_gt is not None and downsample_gt > gt.shape[0]:
         raise ValueError("downsample_gt = %d exceeds the %d ground-truth points" % (downsample_gt, gt.shape[0]))
-    pred, gt = metrics._pair_on_device(pred, gt, ("pred", "gt"))
-    _finite_on_device(pred, "pred")
-    _finite_on_device(gt, "gt")
+    pred, gt = _on_device((pred, gt), ("pred", "gt"))
     if downsample_gt is not None:
         gt = gt[downsampled_indices(gt, downsample_gt)].contiguous()
     n, m = pred.shape[0], gt.shape[0]
@@ -112,7 +98,7 @@ def sinkhorn_metrics(pred, gt, p=2, blur=0.05, iters=100, scaling=None, debias=T
     f, g = _potentials(pred, gt, p, blur, iters, sched)
     r, c = plan_stats(pred, gt, f, g, p, eps)
     ot = _ot(f, g)
-    out = {"ot": ot, "primal_cost": np.float64(metrics._np_sum(c)), "marginal_error": np.float64(metrics._np_sum((r - 1.0 / n).abs())),
+    out = {"ot": ot, "primal_cost": np.float64(metrics.np_sum(c)), "marginal_error": np.float64(metrics.np_sum((r - 1.0 / n).abs())),
            "divergence": None, "eps": np.float64(eps), "n_pre": n, "n_gt": m}
     if debias:
         fa = _potentials(pred, None, p, blur, iters, sched)[0]
@@ -138,20 +124,15 @@ def plan_stats(x, y, f, g, p, eps):
     """(r [n], c [n]) on the device: the row sums of the plan P_ij = a_i b_j exp((f_i + g_j - C_ij)/eps) and of P_ij C_ij."""
     _check_p(p)
     eps = _positive(eps, "eps")
-    x, y = metrics._pair_on_device(x, y, ("x", "y"))
+    x, y = _clouds(x, y)
     n, m = x.shape[0], y.shape[0]
-    if n < 1:
-        raise ValueError("x: an empty cloud")
     if tuple(f.shape) != (n,) or tuple(g.shape) != (m,):
         raise ValueError("plan_stats: expected potentials of shapes (%d,) and (%d,)" % (n, m))
     f, g = f.to(dtype=torch.float64).contiguous(), g.to(dtype=torch.float64).contiguous()
-    lib = _lib.load()
     r = torch.full((n,), float("nan"), dtype=torch.float64, device=x.device)
     c = torch.full((n,), float("nan"), dtype=torch.float64, device=x.device)
-    ws, nbytes = _workspace(lib, n, m, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sapcu_plan_stats_f64(_lib.ptr(x), n, _lib.ptr(y), m, _lib.ptr(f), _lib.ptr(g), int(p), eps, _lib.ptr(r), _lib.ptr(c),
-                                            _lib.ptr(ws), nbytes, _lib.current_stream()))
+    ws, nbytes = _workspace(n, m, x.device)
+    _lib.call("sapcu_plan_stats_f64", x.device, x, n, y, m, f, g, int(p), eps, r, c, ws, nbytes)
     return r, c
 
 
@@ -190,19 +171,19 @@ def _check_settings(p, blur, iters, scaling):
             raise ValueError("scaling: expected a number in (0, 1) or None, got %r" % (scaling,))
 
 
-def _cloud(x, name):
-    """The checks of metrics.py on one input, before anything touches the device."""
-    x = metrics._checked(x, name)
+def _clouds(x, y):
+    """The clouds of one half-step on one device; y must hold a point, then x."""
+    x, y = _inputs.on_device(((x, "x"), (y, "y")), min_rows=(0, 1))
     if x.shape[0] < 1:
-        raise ValueError("%s: an empty cloud" % name)
-    if not torch.is_tensor(x) and not np.isfinite(x).all():
-        raise ValueError("%s contains NaN or infinity" % name)
-    return x
+        raise ValueError("x: an empty cloud")
+    return x, y
 
 
-def _finite_on_device(x, name):
-    if not bool(torch.isfinite(x).all()):
-        raise ValueError("%s contains NaN or infinity" % name)
+def _on_device(given, names):
+    """Inputs that passed ``_inputs.checked`` one after the other, uploaded, the device tensors among them tested for NaN."""
+    out = _inputs.upload(given)
+    _inputs.finite_on_device(given, out, names)
+    return out
 
 
 def _diameter(x, y):
@@ -212,29 +193,24 @@ def _diameter(x, y):
     return float(np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]))
 
 
-def _workspace(lib, n, m, dev):
-    nbytes = int(lib.sapcu_sinkhorn_workspace_bytes(n, m))
-    if nbytes < 0:
-        raise ValueError("sinkhorn: clouds of %d and %d points are outside the supported range" % (n, m))
-    return torch.zeros((nbytes,), dtype=torch.uint8, device=dev), nbytes
+def _workspace(n, m, dev):
+    return _lib.workspace("sapcu_sinkhorn_workspace_bytes", (n, m), dev,
+                          "sinkhorn: clouds of %d and %d points are outside the supported range" % (n, m))
 
 
 def _potentials(x, y, p, blur, iters, sched):
     """The loop on checked, contiguous f64 device clouds (y None: the symmetric problem); only enqueues."""
-    lib = _lib.load()
     n = x.shape[0]
     m = n if y is None else y.shape[0]
     dev = x.device
     f = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
     g = None if y is None else torch.full((m,), float("nan"), dtype=torch.float64, device=dev)
-    ws, nbytes = _workspace(lib, n, m, dev)
+    ws, nbytes = _workspace(n, m, dev)
     arr = (ctypes.c_double * max(len(sched), 1))(*sched)
-    with torch.cuda.device(dev):
-        _lib.check(lib.sapcu_sinkhorn_f64(_lib.ptr(x), n, _lib.ptr(y), m, int(p), arr, len(sched), float(blur) ** p, int(iters), _lib.ptr(f),
-                                          _lib.ptr(g), _lib.ptr(ws), nbytes, _lib.current_stream()))
+    _lib.call("sapcu_sinkhorn_f64", dev, x, n, y, m, int(p), arr, len(sched), float(blur) ** p, int(iters), f, g, ws, nbytes)
     return (f, f) if y is None else (f, g)
 
 
 def _ot(f, g):
     """<a, f> + <b, g> for uniform weights, sums in numpy's order."""
-    return np.float64(metrics._np_sum(f)) / f.numel() + np.float64(metrics._np_sum(g)) / g.numel()
+    return np.float64(metrics.np_sum(f)) / f.numel() + np.float64(metrics.np_sum(g)) / g.numel()

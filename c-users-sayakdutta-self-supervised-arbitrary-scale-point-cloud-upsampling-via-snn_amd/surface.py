@@ -10,10 +10,12 @@ bit (tests/golden/surface_sample.npz).
 
 No CPU path: the HIP library and a device are required.
 """
+import functools
+
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 
 MAX_N = 4096
 
@@ -87,10 +89,10 @@ def build_surface_tables(meshes, device=None, names=None):
         faces.append(np.ascontiguousarray(f).astype(np.int32))
     vcount, fcount = [len(v) for v in verts], [len(f) for f in faces]
     S, tv, tf = len(meshes), sum(vcount), sum(fcount)
-    lib = _lib.load()
-    nbytes = int(lib.sapcu_surface_tables_workspace_bytes(S, tf))
-    if nbytes < 0 or tv >= 2 ** 31:
-        raise ValueError("build_surface_tables: %d meshes with %d vertices and %d faces are outside the range of the call" % (S, tv, tf))
+    refusal = "build_surface_tables: %d meshes with %d vertices and %d faces are outside the range of the call" % (S, tv, tf)
+    if tv >= 2 ** 31:
+        raise ValueError(refusal)
+    ws, nbytes = _lib.workspace("sapcu_surface_tables_workspace_bytes", (S, tf), dev, refusal)
     up = lambda a: torch.from_numpy(a).to(dev)
     vertices, tri = up(np.concatenate(verts)), up(np.concatenate(faces))
     vert_off = up(np.concatenate([[0], np.cumsum(vcount)]).astype(np.int64))
@@ -99,11 +101,8 @@ def build_surface_tables(meshes, device=None, names=None):
     cdf = torch.zeros((tf,), dtype=torch.float64, device=dev)
     area_sum = torch.zeros((S,), dtype=torch.float32, device=dev)
     prob_sum = torch.zeros((S,), dtype=torch.float64, device=dev)
-    ws = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(lib.sapcu_surface_tables_f32(p(vertices), p(vert_off), tv, p(tri), p(face_off), tf, S, p(face_normals), p(cdf),
-                                                p(area_sum), p(prob_sum), p(ws), nbytes, _lib.current_stream()))
+    _lib.call("sapcu_surface_tables_f32", dev, vertices, vert_off, tv, tri, face_off, tf, S, face_normals, cdf, area_sum, prob_sum, ws,
+              nbytes)
     atol = float(np.sqrt(np.finfo(np.float32).eps))
     for name, ps, area in zip(names, prob_sum.tolist(), area_sum.tolist()):
         if not np.isfinite(ps) or abs(ps - 1.0) > atol:
@@ -125,19 +124,7 @@ def sample_surface(tables, mesh_idx, n, u, r1, r2, validate=True):
         raise ValueError("n: need 1 <= n <= %d points, got %d" % (MAX_N, n))
     dev = tables.device
 
-    def dev_tensor(t, name, dtype, shape):
-        if not torch.is_tensor(t):
-            raise ValueError("%s: expected a device tensor" % name)
-        if not t.is_cuda:
-            raise RuntimeError("%s: a CPU tensor (there is no CPU path)" % name)
-        if t.device != dev:
-            raise ValueError("%s: on %s, the tables are on %s" % (name, t.device, dev))
-        if t.dim() != len(shape) or any(w is not None and s != w for s, w in zip(t.shape, shape)):
-            raise ValueError("%s: expected shape %s, got %s" % (name, list(shape), list(t.shape)))
-        if dtype.is_floating_point != t.dtype.is_floating_point:
-            raise ValueError("%s: expected %s, got %s" % (name, dtype, t.dtype))
-        return t.to(dtype).contiguous()
-
+    dev_tensor = functools.partial(_inputs.device_tensor, dev, "the tables")
     mesh_idx = dev_tensor(mesh_idx, "mesh_idx", torch.int64, (None,))
     b, S = mesh_idx.shape[0], len(tables)
     u = dev_tensor(u, "u", torch.float64, (b, n))
@@ -154,9 +141,7 @@ def sample_surface(tables, mesh_idx, n, u, r1, r2, validate=True):
     faces = torch.full((b, n), -1, dtype=torch.int32, device=dev)
     if b == 0:
         return points, normals, faces
-    lib, p, t = _lib.load(), _lib.ptr, tables
-    with torch.cuda.device(dev):
-        _lib.check(lib.sapcu_surface_sample_f32(p(t.vertices), p(t.vert_off), t.vertices.shape[0], p(t.faces), p(t.face_off),
-                                                t.faces.shape[0], p(t.face_normals), p(t.cdf), S, p(mesh_idx), b, n, p(u), p(r1), p(r2),
-                                                p(points), p(normals), p(faces), _lib.current_stream()))
+    t = tables
+    _lib.call("sapcu_surface_sample_f32", dev, t.vertices, t.vert_off, t.vertices.shape[0], t.faces, t.face_off, t.faces.shape[0],
+              t.face_normals, t.cdf, S, mesh_idx, b, n, u, r1, r2, points, normals, faces)
     return points, normals, faces

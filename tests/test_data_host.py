@@ -4,16 +4,15 @@ tie-freeness, the split arithmetic, the clamp of k, the argument errors that nee
 that come before any launch."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import data_ref as R
+import abi_tables
 from conftest import ROOT, golden
 
-HEADER = os.path.join(ROOT, "include", "sapcu_data.h")
 FD_CASES = ("fd_val0", "fd_val1", "fd_train0", "fd_train1")
 FN_CASES = ("fn_val", "fn_train")
 FD_K, FN_K = 32, 12
@@ -22,10 +21,8 @@ ROTATION_ULPS = 2          # the plain-order rotation against the reference's BL
 
 
 def header_entry_points():
-    """{name: argument list} of include/sapcu_data.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+    """{name: argument list} of include/sapcu_data.h."""
+    return abi_tables.header_entry_points("sapcu_data.h")
 
 
 def test_the_header_declares_exactly_the_seventh_table():

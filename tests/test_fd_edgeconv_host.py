@@ -1,22 +1,17 @@
 """The factored EdgeConv training op and the AMP trainer of fd (row f-5), the part that needs no GPU: the fourth export table
 against include/sapcu_fd_edgeconv.h, argument refusals before any launch, the sizers, the form context and AmpTrainer's options."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 import sapcu_amd
-from conftest import ROOT
-
-FD_EDGECONV_HEADER = os.path.join(ROOT, "include", "sapcu_fd_edgeconv.h")
+import abi_tables
 
 
 def fd_edgeconv_header_entry_points():
-    """{name: argument list} of include/sapcu_fd_edgeconv.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    text = re.sub(r"/\*.*?\*/", " ", open(FD_EDGECONV_HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_[a-zA-Z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)}
+    """{name: argument list} of include/sapcu_fd_edgeconv.h."""
+    return abi_tables.header_entry_points("sapcu_fd_edgeconv.h")
 
 
 def test_fd_edgeconv_exports_equal_the_header_and_the_other_tables_are_untouched():

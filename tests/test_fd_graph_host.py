@@ -2,23 +2,20 @@
 include/sapcu_train_step.h, sapcu_multi_select's refusals before any launch, what train_step.GraphedTrainStep — one class under the
 names fn_trainer.GraphedTrainStep and fd_trainer.GraphedTrainStep — refuses before it captures anything, and that it knows no network."""
 import ctypes
-import os
-import re
 import subprocess
 import sys
 
 import pytest
 import torch
 
+import abi_tables
 from conftest import ROOT
 
-TRAIN_STEP_HEADER = os.path.join(ROOT, "include", "sapcu_train_step.h")
 
 
 def train_step_header_entry_points():
-    """{name: argument list} of include/sapcu_train_step.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    text = re.sub(r"/\*.*?\*/", " ", open(TRAIN_STEP_HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_[a-zA-Z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)}
+    """{name: argument list} of include/sapcu_train_step.h."""
+    return abi_tables.header_entry_points("sapcu_train_step.h")
 
 
 def test_train_step_exports_equal_the_header_and_the_other_tables_are_untouched():

@@ -1,23 +1,20 @@
 """fd training (row f-5), the part that needs no GPU: the trainable subclass's interface, the third export table against its header,
 argument refusals before any launch, the synthetic loader and the trainer's metric arithmetic."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import sapcu_amd
-from conftest import FD_KW, ROOT, golden
+import abi_tables
+from conftest import FD_KW, golden
 
-FD_TRAIN_HEADER = os.path.join(ROOT, "include", "sapcu_fd_train.h")
 
 
 def fd_train_header_entry_points():
-    """include/sapcu_fd_train.h parsed the way tests/test_guarded.py parses sapcu.h."""
-    text = re.sub(r"/\*.*?\*/", " ", open(FD_TRAIN_HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_[a-zA-Z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S)}
+    """{name: argument list} of include/sapcu_fd_train.h."""
+    return abi_tables.header_entry_points("sapcu_fd_train.h")
 
 
 def test_trainable_subclass_keeps_the_state_dict_layout_of_the_reference():

@@ -10,7 +10,6 @@ the seeds left in HBM — the same seeds in the same order with the same 6-decim
 import ctypes
 import hashlib
 import os
-import re
 import socket
 import subprocess
 import sys
@@ -19,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_tables
 from conftest import ROOT, golden
 import gpu_utils as U
 
@@ -169,18 +169,12 @@ def test_device_seeds_determinism_capacity_and_table_refusals():
 
 
 # ================================================================================================ 5: the memory contract
-SEEDS_HEADER = os.path.join(ROOT, "include", "sapcu_seeds.h")
 SEED_CASES, SEED_REFUSALS = [], []
 
 
 def seeds_header_entry_points():
-    """include/sapcu_seeds.h parsed the way tests/test_guarded.py parses sapcu.h."""
-    text = open(SEEDS_HEADER).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(sapcu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = m.group(2)
-    return out
+    """{name: argument list} of include/sapcu_seeds.h."""
+    return abi_tables.header_entry_points("sapcu_seeds.h")
 
 
 def _seed_case(name, cloud_fn, cell, ws_offset):

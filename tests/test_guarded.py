@@ -1,14 +1,12 @@
 """CPU tests of the bounds harness itself (tests/guarded.py), the header coverage gate and the host seed generator under
 guards.  The stand-in "kernels" here are torch indexing on CPU tensors; no deliberately bad kernel ever runs on a GPU."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, golden
+from conftest import golden
 from guarded import Arena, GuardDamage, MIN_BAND, guarded
 
 
@@ -145,13 +143,7 @@ EXEMPT = {
 }
 
 
-def header_entry_points():
-    text = open(os.path.join(ROOT, "include", "sapcu.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(sapcu_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        out[m.group(1)] = m.group(2)
-    return out
+from abi_tables import header_entry_points                # include/sapcu.h by default: the table this gate covers
 
 
 def uncovered_entry_points(covered):

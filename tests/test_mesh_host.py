@@ -4,7 +4,6 @@ CGAL tool (tests/golden/mesh_p2f.npz) and against exact rational arithmetic, reg
 OFF reader."""
 import ctypes
 import os
-import re
 from fractions import Fraction
 
 import numpy as np
@@ -12,17 +11,15 @@ import pytest
 import torch
 
 import mesh_ref as M
+import abi_tables
 from conftest import ROOT, golden
 
-HEADER = os.path.join(ROOT, "include", "sapcu_mesh.h")
 CASES = ("ico", "box", "sheet", "torus")
 
 
 def header_entry_points():
-    """{name: argument list} of include/sapcu_mesh.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+    """{name: argument list} of include/sapcu_mesh.h."""
+    return abi_tables.header_entry_points("sapcu_mesh.h")
 
 
 def test_the_header_declares_exactly_the_eighth_table():

@@ -3,23 +3,20 @@ script (tests/golden/cloud_metrics.npz) against a numpy restatement of the stati
 the argument errors that need no device, and the refusals of the C entry point that come before any launch."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_tables
 from conftest import ROOT, golden
 
-HEADER = os.path.join(ROOT, "include", "sapcu_metrics.h")
 THRESHOLDS = (1e-2, 2e-2)
 
 
 def header_entry_points():
-    """{name: argument list} of include/sapcu_metrics.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+    """{name: argument list} of include/sapcu_metrics.h."""
+    return abi_tables.header_entry_points("sapcu_metrics.h")
 
 
 def test_the_header_declares_exactly_the_sixth_table():

@@ -4,7 +4,6 @@ before any launch, the numpy definition (tests/normals_ref.py) against LAPACK an
 ``normal_metrics`` against numpy."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import normals_ref as R
+import abi_tables
 from conftest import GOLDEN, ROOT
 
 HEADER = os.path.join(ROOT, "include", "sapcu_normals.h")
@@ -21,11 +21,9 @@ OTHER_HEADERS = ("sapcu.h", "sapcu_seeds.h", "sapcu_fd_train.h", "sapcu_fd_edgec
 EPS = 2.0 ** -52
 
 
-def header_entry_points(path=HEADER):
-    """{name: argument list} of a header (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+def header_entry_points():
+    """{name: argument list} of include/sapcu_normals.h."""
+    return abi_tables.header_entry_points("sapcu_normals.h")
 
 
 def test_the_header_declares_exactly_the_twelfth_table():

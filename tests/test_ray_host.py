@@ -3,26 +3,23 @@ points that come before any launch, the numpy definition (tests/ray_ref.py) agai
 of the unit box, watertightness, and the numpy restatement of fd's ray sampler."""
 import ctypes
 import os
-import re
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import ray_ref as R
+import abi_tables
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "sapcu_ray.h")
 NAMES = {"sapcu_ray_mesh_workspace_bytes", "sapcu_ray_mesh_f64", "sapcu_ray_fd_samples_workspace_bytes", "sapcu_ray_fd_samples_f64"}
 OTHER_HEADERS = ("sapcu.h", "sapcu_seeds.h", "sapcu_fd_train.h", "sapcu_fd_edgeconv.h", "sapcu_train_step.h", "sapcu_metrics.h",
                  "sapcu_data.h", "sapcu_mesh.h", "sapcu_surface.h", "sapcu_sinkhorn.h")
 
 
-def header_entry_points(path=HEADER):
-    """{name: argument list} of a header (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+def header_entry_points():
+    """{name: argument list} of include/sapcu_ray.h."""
+    return abi_tables.header_entry_points("sapcu_ray.h")
 
 
 def test_the_header_declares_exactly_the_eleventh_table():

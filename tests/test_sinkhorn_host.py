@@ -3,13 +3,13 @@
 refusals of the C entry points that come before any launch, and the argument errors of the Python layer that need no device."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import sinkhorn_ref as R
+import abi_tables
 from conftest import ROOT, golden
 
 HEADER = os.path.join(ROOT, "include", "sapcu_sinkhorn.h")
@@ -17,10 +17,8 @@ _CACHE = {}
 
 
 def header_entry_points():
-    """{name: argument list} of include/sapcu_sinkhorn.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+    """{name: argument list} of include/sapcu_sinkhorn.h."""
+    return abi_tables.header_entry_points("sapcu_sinkhorn.h")
 
 
 def _cases():

@@ -5,16 +5,15 @@ the sizer and the refusals of the C entry points that come before any launch, ``
 loader, and the argument errors of the Python layer that need no device."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 import data_ref as R
 import surface_ref as SR
+import abi_tables
 from conftest import ROOT, golden
 
-HEADER = os.path.join(ROOT, "include", "sapcu_surface.h")
 MESHES = ("icosphere", "torus", "degenerate", "polygons")
 ITEMS = ("item_train", "item_val")
 N, PATCHES, K = 512, 64, 12
@@ -22,10 +21,8 @@ F32 = np.float32
 
 
 def header_entry_points():
-    """{name: argument list} of include/sapcu_surface.h (comments stripped, every `sapcu_xxx(...);` declaration)."""
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(sapcu_\w+)\s*\(([^;{]*)\)\s*;", text)}
+    """{name: argument list} of include/sapcu_surface.h."""
+    return abi_tables.header_entry_points("sapcu_surface.h")
 
 
 def _case(g, name):
