@@ -17,6 +17,9 @@ Public surface = the reference's own interface for this path:
   sample_fd_rays, as_fd_npz, is_watertight, FdRayPatches       truth of fd's directed distance, fd's ray samples from meshes)
   pca_normals, normal_angles, normal_metrics,                 (``normals``: PCA normals of a cloud and the angular error of normals
   cloud_normal_metrics, evaluate_normals_file                  on the device: fn's score, ground-truth normals, surface quality)
+  geodesic_disks, disk_radii, uniformity_seeds,               (``uniformity``: how evenly a cloud covers its mesh, the NUC figures
+  uniformity_metrics, dataset_uniformity, read_seeds,          of the PU-GAN protocol from exact geodesic disks on the device)
+  write_seeds, evaluate_uniformity_file
 Importing the package never touches the GPU; the HIP library is loaded on first use and its
 absence raises ``SapcuLibraryError`` (no CPU fallback exists).
 """
@@ -31,6 +34,8 @@ from .data import build_patches, PU1KPatches, MeshPatches, MeshSurfacePatches, F
 from .surface import build_surface_tables, sample_surface  # noqa: F401
 from .ray import ray_to_mesh, signed_ray_distance, ray_metrics, sample_fd_rays, as_fd_npz, is_watertight  # noqa: F401
 from .normals import pca_normals, normal_angles, normal_metrics, cloud_normal_metrics, evaluate_normals_file  # noqa: F401
+from .uniformity import (geodesic_disks, disk_radii, uniformity_seeds, uniformity_metrics, dataset_uniformity, read_seeds,  # noqa: F401
+                         write_seeds, evaluate_uniformity_file)
 
 __all__ = ["ImprovedSNNNormalEstimation", "EnhancedSNNDistanceEstimation", "TrainableSNNDistanceEstimation", "Generator3D6",
            "SNNPointCloudGenerator", "SapcuError", "SapcuLibraryError"]

@@ -212,7 +212,21 @@ TABLES[None] = _INTERNAL_SIGNATURES = {
     "sapcu_internal_ray_mesh_tuned": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
                                               c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64),
                                               c_void_p]),
+    # sapcu_geodesic_disks_f64 (csrc/sapcu_geodesic.h) with a smaller window cap and a shorter workspace queue: tests/test_gpu_uniformity.py
+    "sapcu_internal_geodesic_disks_limited": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                      c_int64, POINTER(c_double), c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                                      c_void_p, c_int64, POINTER(c_int64), c_void_p]),
 }
+# csrc/sapcu_geodesic.h: geodesic disks on a mesh, the counts behind the uniformity figure (sapcu_amd/uniformity.py).  radii_host is a
+# HOST double[nr], info_host a HOST int64[8].  Bound by load() like a table; kept beside TABLES because tests/abi_tables.py holds
+# the list of TABLES' headers and of include/ closed (moving the header there is one entry in that list)
+GEODESIC_SIGNATURES = {
+    "sapcu_geodesic_disks_workspace_bytes": (c_int64, [c_int64] * 5),
+    "sapcu_geodesic_disks_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                         POINTER(c_double), c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64),
+                                         c_void_p]),
+}
+GEODESIC_EXPORTS = tuple(GEODESIC_SIGNATURES)
 _lib = None
 
 
@@ -230,7 +244,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in ((name, sig) for table in TABLES.values() for name, sig in table.items()):
+    for name, (res, args) in ((name, sig) for table in list(TABLES.values()) + [GEODESIC_SIGNATURES] for name, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

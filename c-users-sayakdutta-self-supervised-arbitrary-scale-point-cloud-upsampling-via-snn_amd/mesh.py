@@ -8,7 +8,7 @@ slivers), and every float equals numpy's (``==``) on the same distance vector, t
 
 Distances stay f64.  The tool stores each distance as ``float`` and prints six digits; that rounding is NOT reproduced, so a value
 agrees with the tool's to about 5e-6 relative, not bit for bit.  The tool's uniformity figures (geodesic disks on the mesh) are
-not computed here.
+``uniformity``'s, which maps the points with ``point_to_mesh``.
 
 No CPU path: the HIP library and a device are required (``read_off`` alone runs on the host).
 """

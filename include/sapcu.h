@@ -52,7 +52,9 @@ typedef enum {
     SAPCU_ERR_ARG = -1,        /* bad pointer / size / hyper-parameter */
     SAPCU_ERR_WORKSPACE = -2,  /* workspace too small (see *_workspace_bytes) */
     SAPCU_ERR_HIP = -3,        /* a HIP runtime call or launch failed */
-    SAPCU_ERR_UNSUPPORTED = -4 /* legal in the reference, not built here (e.g. use_snn_decoder) */
+    SAPCU_ERR_UNSUPPORTED = -4, /* legal in the reference, not built here (e.g. use_snn_decoder) */
+    SAPCU_ERR_MESH = -5,       /* sapcu_geodesic_disks_f64: the mesh is no oriented 2-manifold (sapcu_mesh.h) */
+    SAPCU_ERR_LIMIT = -6       /* sapcu_geodesic_disks_f64: a seed reached its window cap or outgrew the workspace queue */
 } sapcu_status;
 
 typedef struct sapcu_model* sapcu_model_t;
