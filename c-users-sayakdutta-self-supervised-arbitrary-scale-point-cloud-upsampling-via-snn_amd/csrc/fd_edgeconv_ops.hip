@@ -12,25 +12,21 @@
 //                                                            the inverse neighbour table in LDS) and grad_a (over its own).
 // All the sources of a destination p share s[p], so  sum y_hat  over them is  invstd * (deg (s[p] - mean) - sum a[source])  and
 // sum over a point's own edges is  invstd * (sum s[nbr] - cnt (a[i] + mean)):  the backward gathers rows of a, gz and arg-max,
-// it does not evaluate y per edge.  No float atomics: column sums go through per-workgroup f64 partials added in ascending
-// workgroup order, every destination's sources are visited in ascending edge order.
+// it does not evaluate y per edge.  No float atomics: column sums go through per-workgroup f64 partials (fold_groups,
+// train_common.h) added in ascending workgroup order, every destination's sources are visited in ascending edge order
+// (inverse_table_build, train_common.h).
 //
 // Tiling: a workgroup owns 64 channels (one lane each, so every gathered row is one coalesced 256-byte read) — s and a of a
 // whole patch at block 3 (100 x 512 x 4 B each) stay in L2, LDS holds only the backward's inverse table.
 #include "common.h"
 #include "ops.h"
+#include "train_common.h"
 #include "../../include/sapcu_fd_edgeconv.h"
 
 namespace sapcu {
 
 constexpr int EC_STAT_PTS = 16;        // points per workgroup of the statistics pass (each walks its kk neighbours)
 constexpr int EC_GZ_PTS = 64;          // points per workgroup of the backward's arg-max pass
-
-// (y - mean) * invstd * gamma + beta, LeakyReLU(0.2): the arithmetic of bn_lrelu in fd_train_ops.hip, operation for operation
-__device__ __forceinline__ float ec_bn_lrelu(float y, float mu, float is, float ga, float be) {
-    const float z = (y - mu) * is * ga + be;
-    return z > 0.f ? z : z * 0.2f;
-}
 
 // y of edge (pt, neighbour nb) in channel c: s[nb] - a[pt], s = a + b formed in f32; 0 for an index outside the patch
 __device__ __forceinline__ float ec_edge_y(const float* __restrict__ patch_ab, int nb, int m, int ch, int c, float a_i) {
@@ -43,11 +39,10 @@ __device__ __forceinline__ float ec_edge_y(const float* __restrict__ patch_ab, i
 __global__ __launch_bounds__(256) void ec_stats_partial_kernel(const float* __restrict__ ab, const int32_t* __restrict__ idx, int64_t pts,
                                                                int m, int kk, int ch, double* __restrict__ partial /*[gridDim.x][2][ch]*/,
                                                                int* __restrict__ bad) {
-    __shared__ double red[2][4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool live = c < ch;
-    double s0 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};
     for (int q = g; q < EC_STAT_PTS; q += 4) {
         const int64_t pt = (int64_t)blockIdx.x * EC_STAT_PTS + q;
         if (pt >= pts) break;
@@ -59,17 +54,15 @@ __global__ __launch_bounds__(256) void ec_stats_partial_kernel(const float* __re
             const int nb = ip[j];
             nbad += (nb < 0 || nb >= m) ? 1 : 0;
             const float y = live ? ec_edge_y(pab, nb, m, ch, c, a_i) : 0.f;
-            s0 += (double)y;
-            s1 += (double)y * (double)y;
+            s[0] += (double)y;
+            s[1] += (double)y * (double)y;
         }
         if (bad && blockIdx.y == 0 && lane == 0 && nbad) atomicAdd(bad, nbad);
     }
-    red[0][g][lane] = s0;
-    red[1][g][lane] = s1;
-    __syncthreads();
+    fold_groups(s);
     if (g == 0 && live) {
-        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = s[0];
+        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = s[1];
     }
 }
 
@@ -80,35 +73,28 @@ template <int MODE>
 __global__ __launch_bounds__(256) void ec_final_kernel(const double* __restrict__ partial, int64_t nb, int ch, int64_t rows, float eps,
                                                        float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
                                                        double* __restrict__ sums /*[2][ch]*/) {
-    __shared__ double red[2][4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const bool live = c < ch;
-    double s0 = 0.0, s1 = 0.0;
+    double t[2] = {0.0, 0.0};
     if (live) {
         for (int64_t b = g; b < nb; b += 4) {
-            s0 += partial[(b * 2 + 0) * ch + c];
-            s1 += partial[(b * 2 + 1) * ch + c];
+            t[0] += partial[(b * 2 + 0) * ch + c];
+            t[1] += partial[(b * 2 + 1) * ch + c];
         }
     }
-    red[0][g][lane] = s0;
-    red[1][g][lane] = s1;
-    __syncthreads();
+    fold_groups(t);
     if (g != 0 || !live) return;
-    const double t0 = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-    const double t1 = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
     if (MODE == 0) {
-        const double mu = t0 / (double)rows;
-        double var = t1 / (double)rows - mu * mu;                // biased variance, as sapcu_fd_bn_stats
-        if (var < 0.0) var = 0.0;
-        o0[c] = (float)mu;
-        o1[c] = (float)var;
-        o2[c] = (float)(1.0 / sqrt(var + (double)eps));
+        const BnStats s = bn_batch_stats(t[0], t[1], rows, eps);  // as sapcu_fd_bn_stats
+        o0[c] = (float)s.mu;
+        o1[c] = (float)s.var;
+        o2[c] = s.invstd;
     } else {
-        sums[c] = t0;
-        sums[ch + c] = t1;
-        o0[c] = (float)t1;                                       // grad_gamma
-        o1[c] = (float)t0;                                       // grad_beta
+        sums[c] = t[0];
+        sums[ch + c] = t[1];
+        o0[c] = (float)t[1];                                     // grad_gamma
+        o1[c] = (float)t[0];                                     // grad_beta
     }
 }
 
@@ -125,10 +111,10 @@ __global__ __launch_bounds__(256) void ec_max_fwd_kernel(const float* __restrict
     const int32_t* ip = idx + pt * kk;
     const float a_i = ab[pt * 2 * ch + c];
     const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    float mx = ec_bn_lrelu(ec_edge_y(pab, ip[0], m, ch, c, a_i), mu, is, ga, be);
+    float mx = bn_lrelu(ec_edge_y(pab, ip[0], m, ch, c, a_i), mu, is, ga, be);
     int am = 0;
     for (int j = 1; j < kk; ++j) {
-        const float v = ec_bn_lrelu(ec_edge_y(pab, ip[j], m, ch, c, a_i), mu, is, ga, be);
+        const float v = bn_lrelu(ec_edge_y(pab, ip[j], m, ch, c, a_i), mu, is, ga, be);
         if (v > mx || (v != v && mx == mx)) { mx = v; am = j; }
     }
     out[t] = mx;
@@ -144,11 +130,10 @@ __global__ __launch_bounds__(256) void ec_gz_partial_kernel(const float* __restr
                                                             const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, float* __restrict__ gzv,
                                                             double* __restrict__ partial /*[gridDim.x][2][ch]*/) {
-    __shared__ double red[2][4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool live = c < ch;
-    double s0 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};
     if (live) {
         const float mu = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
         for (int q = g; q < EC_GZ_PTS; q += 4) {
@@ -158,22 +143,20 @@ __global__ __launch_bounds__(256) void ec_gz_partial_kernel(const float* __restr
             float gz = 0.f, yh = 0.f;
             if (ar >= 0 && ar < kk) {
                 const float y = ec_edge_y(ab + (pt / m) * m * 2 * (int64_t)ch, idx[pt * kk + ar], m, ch, c, ab[pt * 2 * ch + c]);
-                const float z = (y - mu) * is * ga + be;
+                const float z = bn_z(y, mu, is, ga, be);
                 const float go = gout[pt * ch + c];
                 gz = z > 0.f ? go : go * 0.2f;
                 yh = (y - mu) * is;
             }
             gzv[pt * ch + c] = gz;
-            s0 += (double)gz;
-            s1 += (double)gz * (double)yh;
+            s[0] += (double)gz;
+            s[1] += (double)gz * (double)yh;
         }
     }
-    red[0][g][lane] = s0;
-    red[1][g][lane] = s1;
-    __syncthreads();
+    fold_groups(s);
     if (g == 0 && live) {
-        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = s[0];
+        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = s[1];
     }
 }
 
@@ -186,38 +169,14 @@ __global__ __launch_bounds__(256) void ec_bwd_kernel(const float* __restrict__ a
                                                      float* __restrict__ grad_ab, int* __restrict__ bad) {
     extern __shared__ unsigned char ec_smem[];
     const int gr = m * kk;
-    int* dst = reinterpret_cast<int*>(ec_smem);                 // [gr] destination point of each edge (-1: none)
-    int* lst = dst + gr;                                        // [gr] edges ordered by (destination, edge), packed
-    int* off = lst + gr;                                        // [m + 1]
+    const InverseTable tab(ec_smem, gr);                        // the list entries are the edges, packed
+    const int* dst = tab.dst;
+    const int* lst = tab.lst;
+    const int* off = tab.off;
     const int64_t g = blockIdx.x;
     const int tid = threadIdx.x;
-    int nbad = 0;
-    for (int e = tid; e < gr; e += 256) {
-        const int v = idx[g * gr + e];
-        const bool ok = v >= 0 && v < m;
-        dst[e] = ok ? v : -1;
-        nbad += ok ? 0 : 1;
-    }
+    const int nbad = inverse_table_build(tab, m, gr, [&](int e) { return idx[g * gr + e]; }, [&](int e) { return ((e / kk) << 16) | (e % kk); });
     if (nbad && blockIdx.y == 0) atomicAdd(bad, nbad);
-    __syncthreads();
-    for (int t = tid; t < m; t += 256) {
-        int n = 0;
-        for (int e = 0; e < gr; ++e) n += dst[e] == t;
-        off[t + 1] = n;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        off[0] = 0;
-        for (int t = 0; t < m; ++t) off[t + 1] += off[t];
-    }
-    __syncthreads();
-    for (int t = tid; t < m; t += 256) {
-        int w = off[t];
-        for (int i = 0, e = 0; i < m; ++i)
-            for (int j = 0; j < kk; ++j, ++e)
-                if (dst[e] == t) lst[w++] = (i << 16) | j;
-    }
-    __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
     const int c = blockIdx.y * 64 + lane;
     if (c >= ch) return;
@@ -288,12 +247,11 @@ static EcBwdWs ec_bwd_ws_layout(void* base, int64_t pts, int ch) {
     return w;
 }
 
-static size_t ec_table_bytes(int m, int kk) { return ((size_t)2 * m * kk + m + 1) * sizeof(int); }
 // shapes every entry point accepts: the grids fit, the inverse table fits 64 KiB of LDS (so m * kk < 8192 and the packed list
 // entries hold), the flat indices fit int64 with room
 static bool ec_shape_ok(int64_t patches, int m, int kk, int ch, int64_t min_patches) {
     if (patches < min_patches || m < 1 || kk < 1 || ch < 1 || ch > (1 << 20) || patches >= 0x7fffffffLL) return false;
-    if ((int64_t)m * kk > 16384 || ec_table_bytes(m, kk) > 64 * 1024) return false;
+    if ((int64_t)m * kk > 16384 || inverse_table_bytes(m, (int64_t)m * kk) > 64 * 1024) return false;
     const int64_t pts = patches * m;
     return (pts * ch + 255) / 256 < 0x7fffffffLL && ec_blocks(pts, EC_STAT_PTS) < 0x7fffffffLL;
 }
@@ -381,8 +339,8 @@ int sapcu_fd_edgeconv_backward(const float* ab, const int32_t* idx, const float*
     hipLaunchKernelGGL(ec_final_kernel<1>, dim3(tiles), dim3(256), 0, st, L.partial, nb, channels, pts * kk, 0.f, grad_gamma, grad_beta,
                        (float*)nullptr, L.sums);
     SAPCU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ec_bwd_kernel, dim3((unsigned)patches, tiles), dim3(256), ec_table_bytes(m, kk), st, ab, idx, L.gzv, argmax, m, kk,
-                       channels, pts * kk, L.sums, mean, invstd, gamma, grad_ab, bad_count);
+    hipLaunchKernelGGL(ec_bwd_kernel, dim3((unsigned)patches, tiles), dim3(256), inverse_table_bytes(m, (int64_t)m * kk), st, ab, idx, L.gzv, argmax,
+                       m, kk, channels, pts * kk, L.sums, mean, invstd, gamma, grad_ab, bad_count);
     SAPCU_CHECK_LAUNCH();
     return SAPCU_OK;
 }

@@ -7,11 +7,12 @@
 // refractory_decay take no part in any derivative, and threshold_base is reached only through the step that starts from it.
 // The refractory gate is live: with hard spikes `refractory` is exactly 0 until a neuron's first spike.
 //
-// No float atomics: column sums go through per-workgroup partials added in ascending workgroup order, the EdgeConv backward sums
-// every destination's sources in ascending source order (the scheme of scatter_sum_grouped_kernel, train_ops.hip).  All tensors
-// are dense [rows, channels] f32, channel last, except where a pitch is named.
+// No float atomics: column sums go through per-workgroup partials (fold_groups, train_common.h) added in ascending workgroup order,
+// the EdgeConv backward sums every destination's sources in ascending source order (inverse_table_build, train_common.h).  All
+// tensors are dense [rows, channels] f32, channel last, except where a pitch is named.
 #include "common.h"
 #include "ops.h"
+#include "train_common.h"
 #include "../../include/sapcu_fd_train.h"
 
 namespace sapcu {
@@ -19,23 +20,19 @@ namespace sapcu {
 constexpr int NS_ROWS_PER_WG = 64;     // 4 row slabs of 16 rows x 64 channels per 256-thread workgroup
 constexpr int NS_Q = 4;                // parameter gradients per channel: membrane_decay, threshold_base, delta_T, theta_rh
 
-struct StepP {                         // clamped parameters and the clamp masks of the raw ones (torch.clamp passes [min, max])
+struct StepP {                         // clamped parameters (train_common.h; the clamp masks are applied by neuron_step_reduce_kernel)
     float decay, adapt, rdecay, theta0, dT, rh;
-    bool decay_in, dT_in, rh_in;
 };
 
 __device__ __forceinline__ StepP load_step_params(const float* md, const float* ta, const float* rd, const float* tb, const float* dT,
                                                   const float* rh, bool eif, int c) {
     StepP p;
-    p.decay = fminf(fmaxf(md[c], 0.1f), 0.99f);
-    p.decay_in = md[c] >= 0.1f && md[c] <= 0.99f;
-    p.adapt = ta ? fminf(fmaxf(ta[c], 0.001f), 0.1f) : 0.f;
-    p.rdecay = rd ? fminf(fmaxf(rd[c], 0.1f), 0.95f) : 0.f;
+    p.decay = clamp_membrane_decay(md[c]).v;
+    p.adapt = ta ? clamp_threshold_adapt(ta[c]).v : 0.f;
+    p.rdecay = rd ? clamp_refractory_decay(rd[c]).v : 0.f;
     p.theta0 = tb[c];
-    p.dT = eif ? fminf(fmaxf(dT[c], 0.1f), 5.0f) : 0.f;
-    p.rh = eif ? fminf(fmaxf(rh[c], 0.1f), 2.0f) : 0.f;
-    p.dT_in = eif && dT[c] >= 0.1f && dT[c] <= 5.0f;
-    p.rh_in = eif && rh[c] >= 0.1f && rh[c] <= 2.0f;
+    p.dT = eif ? clamp_delta_T(dT[c]).v : 0.f;
+    p.rh = eif ? clamp_theta_rh(rh[c]).v : 0.f;
     return p;
 }
 
@@ -62,14 +59,6 @@ __device__ __forceinline__ StepV step_integrate(float x, float m, float th, floa
     if (EIF) v.mm = __fadd_rn(v.mm, ex);
     v.u = __fsub_rn(v.mm, th);
     return v;
-}
-
-// derivative of the soft surrogate 0.5 N(u) + 0.5 sigmoid(10 u) on clamp(u, +-10) (fd/snn_coder.py:143-155)
-__device__ __forceinline__ float step_surrogate_grad(float u) {
-    if (!(u >= -10.0f && u <= 10.0f)) return 0.f;
-    const float gauss = expf(-0.5f * u * u) * 0.3989422804014327f;
-    const float sg = 1.0f / (1.0f + expf(-10.0f * u));
-    return 0.5f * (-u * gauss) + 0.5f * (10.0f * sg * (1.0f - sg));
 }
 
 template <bool EIF>
@@ -102,7 +91,6 @@ __global__ __launch_bounds__(256) void neuron_step_bwd_kernel(const float* __res
                                                               const float* __restrict__ m_in, const float* __restrict__ th_in,
                                                               const float* __restrict__ r_in, float* __restrict__ gx,
                                                               float* __restrict__ partial /*[gridDim.x][NS_Q][ch]*/) {
-    __shared__ float red[4][NS_Q][64];
     const int lane = threadIdx.x & 63, slab = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool live = c < ch;
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(256) void neuron_step_bwd_kernel(const float* __res
             const int64_t t = row * ch + c;
             const float m = m_in ? m_in[t] : 0.f, th = th_in ? th_in[t] : p.theta0, r = r_in ? r_in[t] : 0.f;
             const StepV v = step_integrate<EIF>(x[t], m, th, r, p);
-            const float a_u = gout[t] * step_surrogate_grad(v.u);      // u = mm - th: d mm = a_u, d th = -a_u
+            const float a_u = gout[t] * surrogate_grad(v.u);      // u = mm - th: d mm = a_u, d th = -a_u
             gx[t] = a_u * v.gate;
             g[0] += a_u * m * (1.0f - r);                              // mm = m*decay*(1-r) + ...
             if (!th_in) g[1] -= a_u;                                   // the threshold IS threshold_base on the first step only
@@ -128,13 +116,10 @@ __global__ __launch_bounds__(256) void neuron_step_bwd_kernel(const float* __res
             }
         }
     }
-#pragma unroll
-    for (int q = 0; q < NS_Q; ++q) red[slab][q][lane] = g[q];
-    __syncthreads();
+    fold_groups(g);
     if (slab == 0 && live) {
 #pragma unroll
-        for (int q = 0; q < NS_Q; ++q)
-            partial[((int64_t)blockIdx.x * NS_Q + q) * ch + c] = ((red[0][q][lane] + red[1][q][lane]) + red[2][q][lane]) + red[3][q][lane];
+        for (int q = 0; q < NS_Q; ++q) partial[((int64_t)blockIdx.x * NS_Q + q) * ch + c] = g[q];
     }
 }
 
@@ -149,11 +134,11 @@ __global__ __launch_bounds__(256) void neuron_step_reduce_kernel(const float* __
     for (int64_t b = 0; b < nblocks; ++b)
 #pragma unroll
         for (int q = 0; q < NS_Q; ++q) s[q] += partial[(b * NS_Q + q) * ch + c];
-    g_md[c] = (md[c] >= 0.1f && md[c] <= 0.99f) ? s[0] : 0.f;
+    g_md[c] = clamp_membrane_decay(md[c]).in ? s[0] : 0.f;
     g_tb[c] = s[1];
     if (eif) {
-        g_dT[c] = (dT[c] >= 0.1f && dT[c] <= 5.0f) ? s[2] : 0.f;
-        g_rh[c] = (rh[c] >= 0.1f && rh[c] <= 2.0f) ? s[3] : 0.f;
+        g_dT[c] = clamp_delta_T(dT[c]).in ? s[2] : 0.f;
+        g_rh[c] = clamp_theta_rh(rh[c]).in ? s[3] : 0.f;
     }
 }
 
@@ -194,44 +179,21 @@ __global__ __launch_bounds__(256) void edge_feature_fwd_kernel(const float* __re
     out[t] = v;
 }
 
-// one workgroup per patch: the inverse neighbour table is built in LDS (destination t's edges in ascending edge order), then every
+// one workgroup per patch: the inverse neighbour table (train_common.h: destination t's edges in ascending edge order), then every
 // (point, channel) is summed by one thread — first minus its own kk edges' difference halves, then its listed edges — and STORED.
 __global__ __launch_bounds__(256) void edge_feature_bwd_kernel(const float* __restrict__ gout, const int32_t* __restrict__ idx, int m,
                                                                int kk, int c, int oc, float* __restrict__ gx, int ldg,
                                                                int* __restrict__ bad) {
     extern __shared__ unsigned char ef_smem[];
     const int gr = m * kk;
-    int* dst = reinterpret_cast<int*>(ef_smem);                 // [gr] destination point of each edge (-1: none)
-    int* lst = dst + gr;                                        // [gr] edges ordered by (destination, edge)
-    int* off = lst + gr;                                        // [m + 1]
+    const InverseTable tab(ef_smem, gr);                        // the list entries are the edges
+    const int* dst = tab.dst;
+    const int* lst = tab.lst;
+    const int* off = tab.off;
     const int64_t g = blockIdx.x;
     const int tid = threadIdx.x;
-    int nbad = 0;
-    for (int e = tid; e < gr; e += 256) {
-        const int v = idx[g * gr + e];
-        const bool ok = v >= 0 && v < m;
-        dst[e] = ok ? v : -1;
-        nbad += ok ? 0 : 1;
-    }
+    const int nbad = inverse_table_build(tab, m, gr, [&](int e) { return idx[g * gr + e]; }, [](int e) { return e; });
     if (nbad) atomicAdd(bad, nbad);
-    __syncthreads();
-    for (int t = tid; t < m; t += 256) {
-        int n = 0;
-        for (int e = 0; e < gr; ++e) n += dst[e] == t;
-        off[t + 1] = n;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        off[0] = 0;
-        for (int t = 0; t < m; ++t) off[t + 1] += off[t];
-    }
-    __syncthreads();
-    for (int t = tid; t < m; t += 256) {
-        int w = off[t];
-        for (int e = 0; e < gr; ++e)
-            if (dst[e] == t) lst[w++] = e;
-    }
-    __syncthreads();
     const float* gb = gout + g * gr * (int64_t)oc;
     float* ob = gx + g * m * (int64_t)ldg;
     for (int64_t q = tid; q < (int64_t)m * c; q += 256) {
@@ -253,17 +215,10 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const double* __restrict_
                                                        float* __restrict__ invstd_out) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= ch) return;
-    const double mu = sums[c] / (double)rows;
-    double var = sums[ch + c] / (double)rows - mu * mu;          // biased variance, as sapcu_bn_train_forward
-    if (var < 0.0) var = 0.0;
-    mean_out[c] = (float)mu;
-    var_out[c] = (float)var;
-    invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
-__device__ __forceinline__ float bn_lrelu(float y, float mu, float is, float ga, float be) {
-    const float z = (y - mu) * is * ga + be;                     // the arithmetic of bn_train_apply_kernel
-    return z > 0.f ? z : z * 0.2f;
+    const BnStats s = bn_batch_stats(sums[c], sums[ch + c], rows, eps);      // as sapcu_bn_train_forward
+    mean_out[c] = (float)s.mu;
+    var_out[c] = (float)s.var;
+    invstd_out[c] = s.invstd;
 }
 
 // one thread per (group, channel): max over the kk rows of the group of LeakyReLU(BN(y)); ties go to the FIRST row, and a NaN among
@@ -302,7 +257,7 @@ __global__ __launch_bounds__(256) void bn_lrelu_max_bwd_kernel(const float* __re
     const int j = (int)(row - g * kk);
     float v = 0.f;
     if (arg[g * ch + c] == j) {
-        const float z = (y[t] - mean[c]) * invstd[c] * gamma[c] + beta[c];
+        const float z = bn_z(y[t], mean[c], invstd[c], gamma[c], beta[c]);
         v = z > 0.f ? gout[g * ch + c] : gout[g * ch + c] * 0.2f;
     }
     gz[t] = v;
@@ -405,7 +360,7 @@ int sapcu_fd_edge_feature_backward(const float* grad_out, const int32_t* idx, in
     SAPCU_CHECK_ARG(grad_out && idx && grad_x && bad_count, "fd_edge_feature_backward: null pointer (bad_count is required)");
     SAPCU_CHECK_ARG(edge_feature_args_ok(patches, m, kk, channels, out_channels) && ld_grad >= channels,
                     "fd_edge_feature_backward: bad shape (need out_channels >= 2 channels, ld_grad >= channels)");
-    const size_t lds = ((size_t)2 * m * kk + m + 1) * sizeof(int);
+    const size_t lds = inverse_table_bytes(m, (int64_t)m * kk);
     SAPCU_CHECK_ARG(lds <= 64 * 1024, "fd_edge_feature_backward: patch too large (%d points x %d neighbours)", m, kk);
     { const int zrc = zero_count(bad_count, (hipStream_t)stream); if (zrc != SAPCU_OK) return zrc; }
     if (patches == 0) return SAPCU_OK;
@@ -427,7 +382,7 @@ int sapcu_fd_bn_stats(const float* y, int64_t rows, int channels, float eps, flo
     SAPCU_CHECK_ARG(workspace_bytes >= sapcu_fd_bn_stats_workspace_bytes(rows, channels), "fd_bn_stats: workspace of %lld bytes, need %lld",
                     (long long)workspace_bytes, (long long)sapcu_fd_bn_stats_workspace_bytes(rows, channels));
     double* sums = nullptr;
-    const int rc = train_column_sums(y, rows, channels, workspace, &sums, (hipStream_t)stream);
+    const int rc = column_sums(0, y, nullptr, rows, channels, nullptr, nullptr, workspace, &sums, (hipStream_t)stream);
     if (rc != SAPCU_OK) return rc;
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)((channels + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sums, rows, channels,
                        eps, mean_out, var_out, invstd_out);

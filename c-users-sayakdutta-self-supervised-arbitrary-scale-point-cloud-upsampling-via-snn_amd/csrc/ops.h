@@ -121,8 +121,10 @@ int launch_fd_temporal(const float* pooled, int T, int64_t b, int emb, const flo
 int launch_fd_tail(const float* x, const float* qkv, int64_t b, int heads, const float* wo_t, const float* bo,
                    const float* lnw, const float* lnb, const float* wh_t, const float* bh, const float* wd,
                    const float* bd, float* attn_out, float* dist, hipStream_t st);
-// train_ops.hip helper shared with fd_train_ops.hip: f64 fixed-order column sums (sum, sum of squares); `ws` holds train_column_sums_bytes
+// train_ops.hip helper shared with fd_train_ops.hip: f64 fixed-order column sums; `ws` holds train_column_sums_bytes.  mode 0: sum of
+// a, sum of a^2 (b, mean, invstd null); mode 1: sum of a, sum of a * (b - mean) * invstd
 int64_t train_column_sums_bytes(int64_t rows, int ch);
-int train_column_sums(const float* a, int64_t rows, int ch, void* ws, double** sums_out, hipStream_t st);
+int column_sums(int mode, const float* a, const float* b, int64_t rows, int ch, const float* mean, const float* invstd, void* ws,
+                double** sums_out, hipStream_t st);
 
 }  // namespace sapcu

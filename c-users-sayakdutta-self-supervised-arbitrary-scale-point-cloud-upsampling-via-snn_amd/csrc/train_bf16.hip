@@ -16,6 +16,7 @@
 // reference's training batch): the step is bound by launch count and the element-wise kernels, not by this kernel.
 #include "common.h"
 #include "gemm_epi.h"
+#include "train_common.h"
 
 namespace sapcu {
 
@@ -128,7 +129,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const float* __restrict_
     }
 }
 
-// out[i] = sum over slabs (ascending) of part[s][i]
+// out[i] = sum over slabs (ascending) of part[s][i]: the last pass of this file's weight and bias gradients and of the f32 weight
+// gradient of train_ops.hip (launch_slab_sum, train_common.h)
 __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ part, int slabs, int64_t count, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
@@ -137,8 +139,15 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__
     out[i] = s;
 }
 
+int launch_slab_sum(const float* part, int slabs, int64_t count, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part, slabs, count, out);
+    SAPCU_CHECK_LAUNCH();
+    return SAPCU_OK;
+}
+
 // column sums of dy [rows, n] in f32 (the bias gradient: not a product, no rounding to bf16): a workgroup sums 64 columns of
-// one row slab (4 row lanes, fixed order); the slab partials are added in slab order by slab_sum_kernel
+// one row slab (4 row lanes, fixed order); the slab partials are added in slab order by slab_sum_kernel.  The four lanes combine as
+// (p0 + p1) + (p2 + p3): NOT the ((p0 + p1) + p2) + p3 of fold_groups (train_common.h) — a different sum, kept as it is
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ dy, int ld, int64_t rows, int n, int64_t slab,
                                                      float* __restrict__ part_out) {
     __shared__ float part[4][64];
@@ -225,17 +234,14 @@ int sapcu_conv1x1_wgrad_bf16(const float* grad_y, int ldy, const float* x, int l
                        (const float*)nullptr, part, (int64_t)k, (int64_t)n * k);
     SAPCU_CHECK_LAUNCH();
     if (slabs > 1) {
-        const int64_t count = (int64_t)n * k;
-        hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part, (int)slabs, count, grad_w);
-        SAPCU_CHECK_LAUNCH();
+        const int rc = launch_slab_sum(part, (int)slabs, (int64_t)n * k, grad_w, st);
+        if (rc != SAPCU_OK) return rc;
     }
     if (grad_bias) {
-        float* cpart = L.cpart;
         hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)cslabs), dim3(256), 0, st, grad_y, ldy, rows, n,
-                           BF_COLSUM_SLAB, cpart);
+                           BF_COLSUM_SLAB, L.cpart);
         SAPCU_CHECK_LAUNCH();
-        hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cpart, (int)cslabs, (int64_t)n, grad_bias);
-        SAPCU_CHECK_LAUNCH();
+        return launch_slab_sum(L.cpart, (int)cslabs, (int64_t)n, grad_bias, st);
     }
     return SAPCU_OK;
 }

@@ -9,10 +9,11 @@
 // One thread = one (row, channel) element: the T-step forward keeps the per-step quantities the reverse sweep needs in
 // registers (T <= 8), the reverse sweep runs in the same thread — no activations are saved between forward and backward,
 // the backward kernel recomputes the T steps from x.  Parameter gradients are summed over rows deterministically:
-// per-workgroup partial sums (fixed order inside a thread column, then across the workgroup's row slabs in LDS) go to a
-// workspace, a second kernel adds the partials in ascending workgroup order.
+// per-workgroup partial sums (fixed order inside a thread column, then across the workgroup's row slabs: fold_groups,
+// train_common.h) go to a workspace, a second kernel adds the partials in ascending workgroup order.
 #include "common.h"
 #include "ops.h"
+#include "train_common.h"
 #include "../../include/sapcu.h"
 
 namespace sapcu {
@@ -25,15 +26,7 @@ struct TrainP {
 };
 
 __device__ __forceinline__ TrainP load_train_params(const float* md, const float* ta, const float* rd, const float* tb, int c) {
-    return TrainP{fminf(fmaxf(md[c], 0.1f), 0.99f), fminf(fmaxf(ta[c], 0.001f), 0.1f), fminf(fmaxf(rd[c], 0.1f), 0.95f), tb[c]};
-}
-
-// soft surrogate value is not needed in training (the forward value is the hard spike); its derivative is
-__device__ __forceinline__ float surrogate_grad(float u) {
-    if (!(u >= -10.0f && u <= 10.0f)) return 0.f;              // torch.clamp passes the gradient on [min, max] only
-    const float gauss = expf(-0.5f * u * u) * 0.3989422804014327f;
-    const float sg = 1.0f / (1.0f + expf(-10.0f * u));
-    return 0.5f * (-u * gauss) + 0.5f * (10.0f * sg * (1.0f - sg));
+    return TrainP{clamp_membrane_decay(md[c]).v, clamp_threshold_adapt(ta[c]).v, clamp_refractory_decay(rd[c]).v, tb[c]};
 }
 
 struct StepRec {      // what the reverse sweep needs from one forward step
@@ -82,7 +75,6 @@ __global__ __launch_bounds__(256) void lif_train_bwd_kernel(const float* __restr
                                                             int64_t rows, int ch, const float* md, const float* ta,
                                                             const float* rd, const float* tb, float* __restrict__ gx,
                                                             float* __restrict__ partial /*[gridDim.x][4][ch]*/) {
-    __shared__ float red[4][4][64];
     const int lane = threadIdx.x & 63, slab = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool live = c < ch;
@@ -137,27 +129,20 @@ __global__ __launch_bounds__(256) void lif_train_bwd_kernel(const float* __restr
             gx[row * ch + c] = a_sp;
         }
     }
-    red[slab][0][lane] = g_decay;
-    red[slab][1][lane] = g_adapt;
-    red[slab][2][lane] = g_rdecay;
-    red[slab][3][lane] = g_theta;
-    __syncthreads();
+    float s[4] = {g_decay, g_adapt, g_rdecay, g_theta};
+    fold_groups(s);
     if (slab == 0 && live) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float s = ((red[0][q][lane] + red[1][q][lane]) + red[2][q][lane]) + red[3][q][lane];
-            partial[((int64_t)blockIdx.x * 4 + q) * ch + c] = s;
-        }
+        for (int q = 0; q < 4; ++q) partial[((int64_t)blockIdx.x * 4 + q) * ch + c] = s[q];
     }
 }
 
 // sums the per-workgroup partials and applies the clamp masks of the raw parameters.  Workgroup = 64 channels x 4 lanes:
-// lane g adds partials g, g+4, ... in ascending order, the four lane sums are added in the order g = 0..3 (deterministic).
+// lane g adds partials g, g+4, ... in ascending order, the four lane sums are added in the order g = 0..3 (fold_groups).
 __global__ __launch_bounds__(256) void lif_train_param_reduce_kernel(const float* __restrict__ partial, int64_t nblocks, int ch,
                                                                      const float* md, const float* ta, const float* rd,
                                                                      float* __restrict__ g_md, float* __restrict__ g_ta,
                                                                      float* __restrict__ g_rd, float* __restrict__ g_tb) {
-    __shared__ float red[4][4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const bool live = c < ch;
@@ -175,15 +160,11 @@ __global__ __launch_bounds__(256) void lif_train_param_reduce_kernel(const float
                 for (int q = 0; q < 4; ++q) s[q] += v[i][q];
         }
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[g][q][lane] = s[q];
-    __syncthreads();
+    fold_groups(s);
     if (g == 0 && live) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] = ((red[0][q][lane] + red[1][q][lane]) + red[2][q][lane]) + red[3][q][lane];
-        g_md[c] = (md[c] >= 0.1f && md[c] <= 0.99f) ? s[0] : 0.f;
-        g_ta[c] = (ta[c] >= 0.001f && ta[c] <= 0.1f) ? s[1] : 0.f;
-        g_rd[c] = (rd[c] >= 0.1f && rd[c] <= 0.95f) ? s[2] : 0.f;
+        g_md[c] = clamp_membrane_decay(md[c]).in ? s[0] : 0.f;
+        g_ta[c] = clamp_threshold_adapt(ta[c]).in ? s[1] : 0.f;
+        g_rd[c] = clamp_refractory_decay(rd[c]).in ? s[2] : 0.f;
         g_tb[c] = s[3];
     }
 }
@@ -199,18 +180,17 @@ constexpr int CR_ROWS = 256;     // rows per workgroup of the column reductions
 // partial[b][q][c] (f64), q = 0: sum of u(row,c), q = 1: sum of u*v.   MODE 0: u = a, v = a (sum, sum of squares)
 //                                                                    MODE 1: u = a (= dz), v = (b - mean) * invstd (= y_hat)
 // Workgroup = 64 channels x 4 row lanes: thread (g = tid >> 6, lane = tid & 63) sums rows r0+g, r0+g+4, ... of its channel
-// (8 loads in flight per round), the 4 lanes' sums are added in the order g = 0..3 through LDS.
+// (8 loads in flight per round), the 4 lanes' sums are added in the order g = 0..3 (fold_groups).
 template <int MODE>
 __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t rows,
                                                           int ch, const float* __restrict__ mean, const float* __restrict__ invstd,
                                                           double* __restrict__ partial) {
-    __shared__ double red[2][4][64];
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int c = blockIdx.y * 64 + lane;
     const bool live = c < ch;
     const int64_t r0 = (int64_t)blockIdx.x * CR_ROWS;
     const int64_t r1 = r0 + CR_ROWS < rows ? r0 + CR_ROWS : rows;
-    double s0 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};
     if (live) {
         const float mu = MODE == 1 ? mean[c] : 0.f, is = MODE == 1 ? invstd[c] : 0.f;
         for (int64_t r = r0 + g; r < r1; r += 32) {
@@ -225,27 +205,24 @@ __global__ __launch_bounds__(256) void col_partial_kernel(const float* __restric
             for (int i = 0; i < 8; ++i) {
                 if (r + 4 * i >= r1) break;
                 const float v = MODE == 0 ? u[i] : (w[i] - mu) * is;
-                s0 += (double)u[i];
-                s1 += (double)u[i] * (double)v;
+                s[0] += (double)u[i];
+                s[1] += (double)u[i] * (double)v;
             }
         }
     }
-    red[0][g][lane] = s0;
-    red[1][g][lane] = s1;
-    __syncthreads();
+    fold_groups(s);
     if (g == 0 && live) {
-        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+        partial[((int64_t)blockIdx.x * 2 + 0) * ch + c] = s[0];
+        partial[((int64_t)blockIdx.x * 2 + 1) * ch + c] = s[1];
     }
 }
 
 __global__ __launch_bounds__(256) void col_final_kernel(const double* __restrict__ partial, int64_t nb, int ch,
                                                         double* __restrict__ sums /*[2][ch]*/) {
-    __shared__ double red[2][4][64];                     // 64 channels x 4 lanes, lane sums combined in the order g = 0..3
-    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;        // 64 channels x 4 lanes, lane sums combined by fold_groups
     const int c = blockIdx.x * 64 + lane;
     const bool live = c < ch;
-    double s0 = 0.0, s1 = 0.0;
+    double s[2] = {0.0, 0.0};
     if (live) {
         for (int64_t b = g; b < nb; b += 16) {
             double u[4], w[4];
@@ -257,17 +234,15 @@ __global__ __launch_bounds__(256) void col_final_kernel(const double* __restrict
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                s0 += u[i];
-                s1 += w[i];
+                s[0] += u[i];
+                s[1] += w[i];
             }
         }
     }
-    red[0][g][lane] = s0;
-    red[1][g][lane] = s1;
-    __syncthreads();
+    fold_groups(s);
     if (g == 0 && live) {
-        sums[c] = ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
-        sums[ch + c] = ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+        sums[c] = s[0];
+        sums[ch + c] = s[1];
     }
 }
 
@@ -279,16 +254,13 @@ __global__ __launch_bounds__(256) void bn_train_apply_kernel(const float* __rest
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= rows * ch) return;
     const int c = (int)(t % ch);
-    const double mu = sums[c] / (double)rows;
-    double var = sums[ch + c] / (double)rows - mu * mu;       // biased variance: what training-mode normalisation uses
-    if (var < 0.0) var = 0.0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
+    const BnStats s = bn_batch_stats(sums[c], sums[ch + c], rows, eps);
     if (t < ch) {
-        mean_out[c] = (float)mu;
-        var_out[c] = (float)var;
-        invstd_out[c] = is;
+        mean_out[c] = (float)s.mu;
+        var_out[c] = (float)s.var;
+        invstd_out[c] = s.invstd;
     }
-    z[t] = (y[t] - (float)mu) * is * gamma[c] + beta[c];
+    z[t] = bn_z(y[t], (float)s.mu, s.invstd, gamma[c], beta[c]);
 }
 
 // dy = gamma * invstd * (dz - sum(dz)/R - y_hat * sum(dz*y_hat)/R);  dgamma = sum(dz*y_hat), dbeta = sum(dz)
@@ -313,7 +285,7 @@ __global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(const float* __
 // Workgroup = 4 waves = one 64x64 tile of dW over one slab of rows; wave (wn, wk) owns a 32x32 block: lane l supplies
 // dY[r + (l>>5)][n0 + wn*32 + (l&31)] and X[r + (l>>5)][k0 + wk*32 + (l&31)] — row-major tensors are already in the
 // operand layout of v_mfma_f32_32x32x2_f32 for this product, no transposition.  Partials [slab][n][k] are summed in slab
-// order by wgrad_reduce_kernel (deterministic).  First version: operands come straight from global memory (L2 absorbs the
+// order by launch_slab_sum (train_common.h; deterministic).  First version: operands come straight from global memory (L2 absorbs the
 // n/64-fold and k/64-fold re-reads); an LDS-staged / larger-tile version is future work.
 typedef float f32x16t __attribute__((ext_vector_type(16)));
 
@@ -351,15 +323,6 @@ __global__ __launch_bounds__(256) void wgrad_partial_kernel(const float* __restr
         const int row = blockIdx.x * 64 + wn * 32 + (e & 3) + 8 * (e >> 2) + 4 * par;
         if (row < n && col < k) out[(int64_t)row * k + col] = acc[e];
     }
-}
-
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, int slabs, int64_t count,
-                                                           float* __restrict__ dw) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    float s = 0.f;
-    for (int b = 0; b < slabs; ++b) s += partial[(int64_t)b * count + t];
-    dw[t] = s;
 }
 
 __global__ __launch_bounds__(256) void colsum_to_float_kernel(const double* __restrict__ sums, int ch, float* __restrict__ out) {
@@ -406,6 +369,25 @@ static WgradWs wgrad_ws_layout(void* base, int64_t rows, int n, int k) {
 // thread per (point, channel); the softmax is recomputed from `a` with the forward kernel's arithmetic.  grad_v is NOT written
 // here: its contributions are exactly the d pe_j values, which scatter_sum_grouped_kernel sums per neighbour row in a fixed
 // order afterwards (round 4; float atomics until then — the one run-to-run difference of a training step).
+
+// the softmax weights of one (point, channel) over its kk neighbours, ar[j * d] = a_j: max and 1 / denominator once, w_j on demand
+// (fn_softmax_agg_kernel's arithmetic, patch_ops.hip)
+struct SoftmaxW {
+    const float* ar;
+    int d;
+    float inv_sqrt_hd, mx, inv_den;
+    __device__ __forceinline__ float e(int j) const { return fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)); }
+    __device__ __forceinline__ float w(int j) const { return __fmul_rn(e(j), inv_den); }
+};
+__device__ __forceinline__ SoftmaxW softmax_weights(const float* ar, int kk, int d, float sqrt_hd) {
+    SoftmaxW s{ar, d, __fdiv_rn(1.0f, sqrt_hd), -__builtin_huge_valf(), 0.f};
+    for (int j = 0; j < kk; ++j) s.mx = fmaxf(s.mx, __fmul_rn(ar[(int64_t)j * d], s.inv_sqrt_hd));
+    float den = 0.f;
+    for (int j = 0; j < kk; ++j) den = __fadd_rn(den, s.e(j));
+    s.inv_den = __fdiv_rn(1.0f, den);
+    return s;
+}
+
 __global__ __launch_bounds__(256) void softmax_agg_bwd_kernel(const float* __restrict__ a, const float* __restrict__ pe,
                                                               const float* __restrict__ v, int ldv, const int32_t* __restrict__ idx,
                                                               const float* __restrict__ gres, int64_t pts, int m, int kk, int d,
@@ -420,27 +402,22 @@ __global__ __launch_bounds__(256) void softmax_agg_bwd_kernel(const float* __res
     const float* pr = pe + pt * kk * d + c;
     const float* kr = keep ? keep + pt * kk * d + c : nullptr;
     const int32_t* ir = idx + pt * kk;
-    const float inv_sqrt_hd = __fdiv_rn(1.0f, sqrt_hd);
-    float mx = -__builtin_huge_valf();
-    for (int j = 0; j < kk; ++j) mx = fmaxf(mx, __fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd));
-    float den = 0.f;
-    for (int j = 0; j < kk; ++j) den = __fadd_rn(den, fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)));
-    const float inv_den = __fdiv_rn(1.0f, den);
+    const SoftmaxW sw = softmax_weights(ar, kk, d, sqrt_hd);
     float res = 0.f;
     for (int j = 0; j < kk; ++j) {
-        float wj = __fmul_rn(fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)), inv_den);
+        float wj = sw.w(j);
         if (kr) wj = __fmul_rn(wj, kr[(int64_t)j * d]);
         res = __fmaf_rn(wj, __fadd_rn(v[(patch_i * m + ir[j]) * ldv + c], pr[(int64_t)j * d]), res);
     }
     const float g = gres[t];
     for (int j = 0; j < kk; ++j) {
-        const float wj = __fmul_rn(fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)), inv_den);
+        const float wj = sw.w(j);
         const float kj = kr ? kr[(int64_t)j * d] : 1.0f;                    // dropout on the softmax weights (fn:383)
         const int64_t nb = patch_i * m + ir[j];
         const float u = __fadd_rn(v[nb * ldv + c], pr[(int64_t)j * d]);
         const float wg = wj * kj * g;
         gpe[(pt * kk + j) * d + c] = wg;
-        ga[(pt * kk + j) * d + c] = wj * g * (kj * u - res) * inv_sqrt_hd;
+        ga[(pt * kk + j) * d + c] = wj * g * (kj * u - res) * sw.inv_sqrt_hd;
     }
 }
 
@@ -459,15 +436,10 @@ __global__ __launch_bounds__(256) void softmax_agg_keep_fwd_kernel(const float* 
     const float* pr = pe + pt * kk * d + c;
     const float* kr = keep + pt * kk * d + c;
     const int32_t* ir = idx + pt * kk;
-    const float inv_sqrt_hd = __fdiv_rn(1.0f, sqrt_hd);
-    float mx = -__builtin_huge_valf();
-    for (int j = 0; j < kk; ++j) mx = fmaxf(mx, __fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd));
-    float den = 0.f;
-    for (int j = 0; j < kk; ++j) den = __fadd_rn(den, fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)));
-    const float inv_den = __fdiv_rn(1.0f, den);
+    const SoftmaxW sw = softmax_weights(ar, kk, d, sqrt_hd);
     float res = 0.f;
     for (int j = 0; j < kk; ++j) {
-        const float wj = __fmul_rn(__fmul_rn(fast_exp(__fsub_rn(__fmul_rn(ar[(int64_t)j * d], inv_sqrt_hd), mx)), inv_den), kr[(int64_t)j * d]);
+        const float wj = __fmul_rn(sw.w(j), kr[(int64_t)j * d]);
         res = __fmaf_rn(wj, __fadd_rn(v[(patch_i * m + ir[j]) * ldv + c], pr[(int64_t)j * d]), res);
     }
     out[t] = res;
@@ -510,9 +482,8 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* __re
 
 // ---- deterministic scatter-add for the patch-structured indices of the training step (round 4).  Every index tensor the step
 // scatters through is grouped: the gr source rows of group g (the m k edge rows of a patch) point into the gs destination rows
-// of the SAME group (the patch's m points).  One workgroup per group: the group's destinations (as local ids) go to LDS, the
-// INVERSE table is built there — destination t's sources in ascending source order, by one thread per destination scanning the
-// gr entries twice (count, then fill behind an exclusive prefix of the counts) — and every (destination, channel) is then summed
+// of the SAME group (the patch's m points).  One workgroup per group: the INVERSE table is built in LDS (inverse_table_build,
+// train_common.h: destination t's sources in ascending source order) and every (destination, channel) is then summed
 // by one thread over its sources in that order and STORED: no atomics, no zeroing, the same bits every run.  (The float
 // atomicAdd form summed in arrival order: the last bits of the gradients, and with hard spikes whole trajectories, differed
 // from run to run.)  LOCAL = true: index32 holds in-patch ids (softmax-aggregate's neighbour table); false: index64 holds global
@@ -523,37 +494,14 @@ __global__ __launch_bounds__(256) void scatter_sum_grouped_kernel(const float* _
                                                                   const int64_t* __restrict__ index64, int gs, int gr, int d,
                                                                   float* __restrict__ gsrc, int ldg, int* __restrict__ bad) {
     extern __shared__ unsigned char sg_smem[];
-    int* dst = reinterpret_cast<int*>(sg_smem);                 // [gr] local destination of each source row (-1: none)
-    int* lst = dst + gr;                                        // [gr] source rows ordered by (destination, source)
-    int* off = lst + gr;                                        // [gs + 1] start of each destination's list
+    const InverseTable tab(sg_smem, gr);                        // the list entries are the source rows
+    const int* lst = tab.lst;
+    const int* off = tab.off;
     const int64_t g = blockIdx.x;
     const int tid = threadIdx.x;
-    int nbad = 0;
-    for (int e = tid; e < gr; e += 256) {
-        const int64_t v = LOCAL ? (int64_t)index32[g * gr + e] : index64[g * gr + e] - g * gs;
-        const bool ok = v >= 0 && v < gs;
-        dst[e] = ok ? (int)v : -1;
-        nbad += ok ? 0 : 1;
-    }
+    const int nbad = inverse_table_build(
+        tab, gs, gr, [&](int e) { return LOCAL ? (int64_t)index32[g * gr + e] : index64[g * gr + e] - g * gs; }, [](int e) { return e; });
     if (nbad && bad) atomicAdd(bad, nbad);
-    __syncthreads();
-    for (int t = tid; t < gs; t += 256) {                       // count
-        int c = 0;
-        for (int e = 0; e < gr; ++e) c += dst[e] == t;
-        off[t + 1] = c;
-    }
-    __syncthreads();
-    if (tid == 0) {                                             // exclusive prefix (gs <= a few hundred)
-        off[0] = 0;
-        for (int t = 0; t < gs; ++t) off[t + 1] += off[t];
-    }
-    __syncthreads();
-    for (int t = tid; t < gs; t += 256) {                       // fill, ascending source order
-        int w = off[t];
-        for (int e = 0; e < gr; ++e)
-            if (dst[e] == t) lst[w++] = e;
-    }
-    __syncthreads();
     const float* gb = gout + g * gr * (int64_t)d;
     float* ob = gsrc + g * gs * (int64_t)ldg;
     for (int64_t q = tid; q < (int64_t)gs * d; q += 256) {
@@ -567,7 +515,7 @@ __global__ __launch_bounds__(256) void scatter_sum_grouped_kernel(const float* _
 static int launch_scatter_sum_grouped(const float* gout, const int32_t* i32, const int64_t* i64, int64_t groups, int gs, int gr, int d,
                                       float* gsrc, int ldg, int* bad, hipStream_t st) {
     if (groups == 0) return SAPCU_OK;
-    const size_t lds = ((size_t)2 * gr + gs + 1) * sizeof(int);
+    const size_t lds = inverse_table_bytes(gs, gr);
     SAPCU_CHECK_ARG(lds <= 64 * 1024 && groups < 0x7fffffffLL, "scatter_sum_grouped: group too large (%d sources, %d destinations)", gr, gs);
     if (i32)
         hipLaunchKernelGGL(scatter_sum_grouped_kernel<true>, dim3((unsigned)groups), dim3(256), lds, st, gout, i32, i64, gs, gr, d, gsrc, ldg, bad);
@@ -608,15 +556,17 @@ __global__ __launch_bounds__(256) void group_max_bwd_kernel(const float* __restr
     gx[t] = arg[g * c + cc] == i ? gout[g * c + cc] : 0.f;
 }
 
-// The f64 fixed-order column sums (sum, sum of squares) for fd_train_ops.hip (ops.h): sums_out [2][ch] lies inside `ws`, which
-// holds train_column_sums_bytes.  The same two launches as the MODE 0 reduction of sapcu_bn_train_forward.
+// The f64 fixed-order column sums of col_partial_kernel<mode> (ops.h; fd_train_ops.hip takes mode 0 through it): sums_out [2][ch]
+// lies inside `ws`, which holds train_column_sums_bytes.
 int64_t train_column_sums_bytes(int64_t rows, int ch) { return (int64_t)colsum_ws_layout(nullptr, rows, ch).bytes; }
-int train_column_sums(const float* a, int64_t rows, int ch, void* ws, double** sums_out, hipStream_t st) {
+int column_sums(int mode, const float* a, const float* b, int64_t rows, int ch, const float* mean, const float* invstd, void* ws,
+                double** sums_out, hipStream_t st) {
     const int64_t nb = col_blocks(rows);
     const ColSumWs L = colsum_ws_layout(ws, rows, ch);
     if (nb > 0) {
-        hipLaunchKernelGGL(col_partial_kernel<0>, dim3((unsigned)nb, (unsigned)((ch + 63) / 64)), dim3(256), 0, st, a, (const float*)nullptr,
-                           rows, ch, (const float*)nullptr, (const float*)nullptr, L.partial);
+        const dim3 grid((unsigned)nb, (unsigned)((ch + 63) / 64));
+        if (mode == 0) hipLaunchKernelGGL(col_partial_kernel<0>, grid, dim3(256), 0, st, a, b, rows, ch, mean, invstd, L.partial);
+        else hipLaunchKernelGGL(col_partial_kernel<1>, grid, dim3(256), 0, st, a, b, rows, ch, mean, invstd, L.partial);
         SAPCU_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(col_final_kernel, dim3((unsigned)((ch + 63) / 64)), dim3(256), 0, st, L.partial, nb, ch, L.sums);
@@ -702,24 +652,6 @@ int64_t sapcu_train_workspace_bytes(int64_t rows, int channels, int k) {
     return (col > wg ? col : wg) + 256;
 }
 
-static int column_sums(int mode, const float* a, const float* b, int64_t rows, int ch, const float* mean, const float* invstd,
-                       void* ws, double** sums_out, hipStream_t st) {
-    const int64_t nb = col_blocks(rows);
-    const ColSumWs L = colsum_ws_layout(ws, rows, ch);
-    double* partial = L.partial;
-    double* sums = L.sums;
-    const dim3 grid((unsigned)(nb > 0 ? nb : 1), (unsigned)((ch + 63) / 64));
-    if (nb > 0) {
-        if (mode == 0) hipLaunchKernelGGL(col_partial_kernel<0>, grid, dim3(256), 0, st, a, b, rows, ch, mean, invstd, partial);
-        else hipLaunchKernelGGL(col_partial_kernel<1>, grid, dim3(256), 0, st, a, b, rows, ch, mean, invstd, partial);
-        SAPCU_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(col_final_kernel, dim3((unsigned)((ch + 63) / 64)), dim3(256), 0, st, partial, nb, ch, sums);
-    SAPCU_CHECK_LAUNCH();
-    *sums_out = sums;
-    return SAPCU_OK;
-}
-
 int sapcu_bn_train_forward(const float* y, int64_t rows, int channels, const float* gamma, const float* beta, float eps,
                            float* z_out, float* mean_out, float* var_out, float* invstd_out, void* workspace,
                            int64_t workspace_bytes, void* stream) {
@@ -777,10 +709,7 @@ int sapcu_conv1x1_wgrad_f32(const float* grad_y, int ldy, const float* x, int ld
     hipLaunchKernelGGL(wgrad_partial_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)((k + 63) / 64), (unsigned)slabs), dim3(256), 0,
                        st, grad_y, ldy, x, ldx, rows, n, k, rps, part);
     SAPCU_CHECK_LAUNCH();
-    const int64_t count = (int64_t)n * k;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, part, slabs, count, grad_w);
-    SAPCU_CHECK_LAUNCH();
-    return SAPCU_OK;
+    return launch_slab_sum(part, slabs, (int64_t)n * k, grad_w, st);
 }
 
 

@@ -43,9 +43,10 @@ def _need_cuda(x, what):
 def _check_patch_shape(M, kk):
     """The EdgeConv backward keeps a patch's inverse neighbour table (2 M kk + M + 1 ints) in LDS: a shape beyond its limit is
     refused here, in the forward, not later inside loss.backward()."""
-    if (2 * M * kk + M + 1) * 4 > EDGE_LDS_LIMIT:
+    need = T.group_lds_bytes(M, M * kk)
+    if need > EDGE_LDS_LIMIT:
         raise ValueError("EdgeConv training op: %d points x %d neighbours per patch need %d bytes of LDS in the backward, the limit is %d"
-                         % (M, kk, (2 * M * kk + M + 1) * 4, EDGE_LDS_LIMIT))
+                         % (M, kk, need, EDGE_LDS_LIMIT))
 
 
 def bad_index_counter(device):
@@ -76,7 +77,6 @@ class _NeuronStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, md, ta, rd, tb, dT, rh, m_in, th_in, r_in, force):
         _need_cuda(x, "neuron_step_train")
-        lib = _lib.load()
         eif = dT is not None
         x = x.contiguous()
         rows, ch = x.shape
@@ -84,10 +84,7 @@ class _NeuronStep(torch.autograd.Function):
         state = [None if s is None else s.contiguous() for s in (m_in, th_in, r_in)]
         force = None if force is None else force.contiguous()
         sp, m, th, r, pre = (torch.empty_like(x) for _ in range(5))
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sapcu_fd_neuron_step_forward(_lib.ptr(x), rows, ch, int(eif), *[_lib.ptr(p) for p in prm],
-                                                        *[_lib.ptr(s) for s in state], _lib.ptr(force), _lib.ptr(sp), _lib.ptr(m),
-                                                        _lib.ptr(th), _lib.ptr(r), _lib.ptr(pre), _lib.current_stream()))
+        _lib.call("sapcu_fd_neuron_step_forward", x.device, x, rows, ch, int(eif), *prm, *state, force, sp, m, th, r, pre)
         ctx.eif, ctx.prm, ctx.state = eif, prm, state
         ctx.save_for_backward(x)
         ctx.mark_non_differentiable(m, th, r, pre)
@@ -95,20 +92,15 @@ class _NeuronStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_sp, *_unused):
-        lib = _lib.load()
         (x,) = ctx.saved_tensors
         rows, ch = x.shape
         md, _, _, tb, dT, rh = ctx.prm
         gx = torch.empty_like(x)
         gmd, gtb = torch.empty_like(md), torch.empty_like(tb)
         gdT, grh = (torch.empty_like(dT), torch.empty_like(rh)) if ctx.eif else (None, None)
-        nbytes = int(lib.sapcu_fd_neuron_step_workspace_bytes(rows, ch))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sapcu_fd_neuron_step_backward(_lib.ptr(x), _lib.ptr(g_sp.contiguous()), rows, ch, int(ctx.eif), _lib.ptr(md),
-                                                         _lib.ptr(tb), _lib.ptr(dT), _lib.ptr(rh), *[_lib.ptr(s) for s in ctx.state],
-                                                         _lib.ptr(gx), _lib.ptr(gmd), _lib.ptr(gtb), _lib.ptr(gdT), _lib.ptr(grh),
-                                                         _lib.ptr(ws), nbytes, _lib.current_stream()))
+        ws, nbytes = T._empty_ws("sapcu_fd_neuron_step_workspace_bytes", (rows, ch), x.device)
+        _lib.call("sapcu_fd_neuron_step_backward", x.device, x, g_sp.contiguous(), rows, ch, int(ctx.eif), md, tb, dT, rh, *ctx.state,
+                  gx, gmd, gtb, gdT, grh, ws, nbytes)
         return gx, gmd, None, None, gtb, gdT, grh, None, None, None, None
 
 
@@ -130,26 +122,21 @@ def _pad32(n):
 def edge_feature_forward(x, idx, out_channels=None):
     """The EdgeConv graph feature as a plain op: x [P*M, C], idx int32 [P, M, kk] -> [P*M*kk, out_channels] = [x[nbr] - x[i] | x[nbr] | 0]."""
     _need_cuda(x, "edge_feature")
-    lib = _lib.load()
     P, M, kk = idx.shape
     _check_patch_shape(M, kk)
     c = x.shape[1]
     oc = 2 * c if out_channels is None else int(out_channels)
     x, idx = x.contiguous(), idx.contiguous()
     out = torch.empty((P * M * kk, oc), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sapcu_fd_edge_feature_forward(_lib.ptr(x), c, _lib.ptr(idx), P, M, kk, c, oc, _lib.ptr(out), None, _lib.current_stream()))
+    _lib.call("sapcu_fd_edge_feature_forward", x.device, x, c, idx, P, M, kk, c, oc, out, None)
     return out
 
 
 def _edge_feature_backward(g, idx, c):
-    lib = _lib.load()
     P, M, kk = idx.shape
     gx = torch.empty((P * M, c), dtype=torch.float32, device=g.device)
     bad = torch.empty((1,), dtype=torch.int32, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.sapcu_fd_edge_feature_backward(_lib.ptr(g), _lib.ptr(idx), P, M, kk, c, g.shape[1], _lib.ptr(gx), c, _lib.ptr(bad),
-                                                      _lib.current_stream()))
+    _lib.call("sapcu_fd_edge_feature_backward", g.device, g, idx, P, M, kk, c, g.shape[1], gx, c, bad)
     bad_index_counter(g.device).add_(bad)
     return gx
 
@@ -170,15 +157,13 @@ def edge_feature(x, idx, out_channels=None):
     return _EdgeFeature.apply(x, idx, out_channels)
 
 
-def _bn_stats(lib, y, eps):
+def _bn_stats(y, eps):
     rows, ch = y.shape
     if rows < 2:
         raise ValueError("BatchNorm in training mode needs more than 1 value per channel (got %d rows)" % rows)
     mean, var, invstd = (torch.empty((ch,), dtype=torch.float32, device=y.device) for _ in range(3))
-    nbytes = int(lib.sapcu_fd_bn_stats_workspace_bytes(rows, ch))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=y.device)
-    _lib.check(lib.sapcu_fd_bn_stats(_lib.ptr(y), rows, ch, float(eps), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(invstd), _lib.ptr(ws),
-                                     nbytes, _lib.current_stream()))
+    ws, nbytes = T._empty_ws("sapcu_fd_bn_stats_workspace_bytes", (rows, ch), y.device)
+    _lib.call("sapcu_fd_bn_stats", y.device, y, rows, ch, float(eps), mean, var, invstd, ws, nbytes)
     return mean, var, invstd
 
 
@@ -204,7 +189,6 @@ class _ConvBnLreluMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, idx, weight, gamma, beta, group, eps, running, reps):
         _need_cuda(x, "conv_bn_lrelu_max")
-        lib = _lib.load()
         dev = x.device
         x = x.contiguous()
         w = weight.detach().reshape(weight.shape[0], -1)
@@ -213,22 +197,20 @@ class _ConvBnLreluMax(torch.autograd.Function):
             raise ValueError("conv_bn_lrelu_max: output channels must be a multiple of 32 (got %d)" % cout)
         w = F.pad(w, (0, _pad32(cin) - cin)).contiguous()
         ga, be = gamma.detach().contiguous(), beta.detach().contiguous()
-        with torch.cuda.device(dev):
-            if idx is not None:
-                idx = idx.contiguous()
-                a = edge_feature_forward(x, idx, w.shape[1])
-            else:
-                a = x if cin == w.shape[1] else F.pad(x, (0, w.shape[1] - cin))
-            rows = a.shape[0]
-            if rows % group:
-                raise ValueError("conv_bn_lrelu_max: %d rows are not whole groups of %d" % (rows, group))
-            y = torch.empty((rows, cout), dtype=torch.float32, device=dev)
-            T._gemm(lib, a, w, None, y)
-            mean, var, invstd = _bn_stats(lib, y, eps)
-            out = torch.empty((rows // group, cout), dtype=torch.float32, device=dev)
-            arg = torch.empty((rows // group, cout), dtype=torch.int32, device=dev)
-            _lib.check(lib.sapcu_fd_bn_lrelu_max_forward(_lib.ptr(y), rows // group, int(group), cout, _lib.ptr(mean), _lib.ptr(invstd),
-                                                         _lib.ptr(ga), _lib.ptr(be), _lib.ptr(out), _lib.ptr(arg), _lib.current_stream()))
+        if idx is not None:
+            idx = idx.contiguous()
+            a = edge_feature_forward(x, idx, w.shape[1])
+        else:
+            a = x if cin == w.shape[1] else F.pad(x, (0, w.shape[1] - cin))
+        rows = a.shape[0]
+        if rows % group:
+            raise ValueError("conv_bn_lrelu_max: %d rows are not whole groups of %d" % (rows, group))
+        y = torch.empty((rows, cout), dtype=torch.float32, device=dev)
+        T._gemm(a, w, None, y)
+        mean, var, invstd = _bn_stats(y, eps)
+        out = torch.empty((rows // group, cout), dtype=torch.float32, device=dev)
+        arg = torch.empty((rows // group, cout), dtype=torch.int32, device=dev)
+        _lib.call("sapcu_fd_bn_lrelu_max_forward", dev, y, rows // group, int(group), cout, mean, invstd, ga, be, out, arg)
         _update_running(running, mean, var, rows, int(reps))
         ctx.save_for_backward(x, w, ga, be, y, mean, invstd, arg)
         ctx.idx, ctx.group, ctx.cin, ctx.wshape = idx, int(group), cin, weight.shape
@@ -236,7 +218,6 @@ class _ConvBnLreluMax(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, w, ga, be, y, mean, invstd, arg = ctx.saved_tensors
         dev = x.device
         rows, cout = y.shape
@@ -244,25 +225,21 @@ class _ConvBnLreluMax(torch.autograd.Function):
         gz, dy = torch.empty_like(y), torch.empty_like(y)
         dgamma, dbeta = torch.empty_like(ga), torch.empty_like(be)
         dw = torch.empty_like(w)
-        ws, nbytes = T._ws(lib, rows, cout, kpad, dev)
+        ws, nbytes = T._empty_ws("sapcu_train_workspace_bytes", (rows, cout, kpad), dev)
         dx = None
-        with torch.cuda.device(dev):
-            st = _lib.current_stream()
-            _lib.check(lib.sapcu_fd_bn_lrelu_max_backward(_lib.ptr(y), _lib.ptr(g.contiguous()), _lib.ptr(arg), rows // ctx.group, ctx.group,
-                                                          cout, _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(ga), _lib.ptr(be), _lib.ptr(gz), st))
-            _lib.check(lib.sapcu_bn_train_backward(_lib.ptr(y), _lib.ptr(gz), rows, cout, _lib.ptr(ga), _lib.ptr(mean), _lib.ptr(invstd),
-                                                   _lib.ptr(dy), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws), nbytes, st))
-            del gz
-            if ctx.idx is not None:
-                a = edge_feature_forward(x, ctx.idx, kpad)
-            else:
-                a = x if ctx.cin == kpad else F.pad(x, (0, kpad - ctx.cin))
-            T._wgrad(lib, dy, a, rows, cout, kpad, dw, None, ws, nbytes, st)
-            del a
-            if ctx.needs_input_grad[0]:
-                da = torch.empty((rows, kpad), dtype=torch.float32, device=dev)
-                T._gemm(lib, dy, w.t().contiguous(), None, da)           # da[r, k] = dy[r, n] . (W^T)[k, n]^T
-                dx = _edge_feature_backward(da, ctx.idx, x.shape[1]) if ctx.idx is not None else da[:, :ctx.cin]
+        _lib.call("sapcu_fd_bn_lrelu_max_backward", dev, y, g.contiguous(), arg, rows // ctx.group, ctx.group, cout, mean, invstd, ga, be, gz)
+        _lib.call("sapcu_bn_train_backward", dev, y, gz, rows, cout, ga, mean, invstd, dy, dgamma, dbeta, ws, nbytes)
+        del gz
+        if ctx.idx is not None:
+            a = edge_feature_forward(x, ctx.idx, kpad)
+        else:
+            a = x if ctx.cin == kpad else F.pad(x, (0, kpad - ctx.cin))
+        T._wgrad(dy, a, rows, cout, kpad, dw, None, ws, nbytes)
+        del a
+        if ctx.needs_input_grad[0]:
+            da = torch.empty((rows, kpad), dtype=torch.float32, device=dev)
+            T._gemm(dy, w.t().contiguous(), None, da)                # da[r, k] = dy[r, n] . (W^T)[k, n]^T
+            dx = _edge_feature_backward(da, ctx.idx, x.shape[1]) if ctx.idx is not None else da[:, :ctx.cin]
         return dx, None, dw[:, :ctx.cin].reshape(ctx.wshape), dgamma, dbeta, None, None, None, None
 
 
@@ -299,53 +276,40 @@ class edgeconv_form(object):
         return False
 
 
-def _count_bad(bad):
-    bad_index_counter(bad.device).add_(bad)
-
-
-def _edgeconv_factored_forward(lib, x, wst, idx, ga, be, eps):
-    """x [P*M, C], wst = [W1 ; W2] [2 cout, C], idx int32 [P, M, kk] -> ab = [x W1^T | x W2^T], mean, var, invstd, out, arg.
-    The caller holds torch.cuda.device(x.device)."""
+def _edgeconv_factored_forward(x, wst, idx, ga, be, eps):
+    """x [P*M, C], wst = [W1 ; W2] [2 cout, C], idx int32 [P, M, kk] -> ab = [x W1^T | x W2^T], mean, var, invstd, out, arg."""
     P, M, kk = idx.shape
     cout, dev = wst.shape[0] // 2, x.device
     ab = torch.empty((P * M, 2 * cout), dtype=torch.float32, device=dev)
-    T._gemm(lib, x, wst, None, ab)
+    T._gemm(x, wst, None, ab)
     mean, var, invstd = (torch.empty((cout,), dtype=torch.float32, device=dev) for _ in range(3))
-    nbytes = int(lib.sapcu_fd_edgeconv_stats_workspace_bytes(P, M, kk, cout))
-    ws = torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)
-    st = _lib.current_stream()
-    _lib.check(lib.sapcu_fd_edgeconv_stats(_lib.ptr(ab), _lib.ptr(idx), P, M, kk, cout, float(eps), _lib.ptr(mean), _lib.ptr(var),
-                                           _lib.ptr(invstd), None, _lib.ptr(ws), nbytes, st))
+    ws, nbytes = T._empty_ws("sapcu_fd_edgeconv_stats_workspace_bytes", (P, M, kk, cout), dev)
+    _lib.call("sapcu_fd_edgeconv_stats", dev, ab, idx, P, M, kk, cout, float(eps), mean, var, invstd, None, ws, nbytes)
     out = torch.empty((P * M, cout), dtype=torch.float32, device=dev)
     arg = torch.empty((P * M, cout), dtype=torch.int32, device=dev)
-    _lib.check(lib.sapcu_fd_edgeconv_max_forward(_lib.ptr(ab), _lib.ptr(idx), P, M, kk, cout, _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(ga),
-                                                 _lib.ptr(be), _lib.ptr(out), _lib.ptr(arg), st))
+    _lib.call("sapcu_fd_edgeconv_max_forward", dev, ab, idx, P, M, kk, cout, mean, invstd, ga, be, out, arg)
     return ab, mean, var, invstd, out, arg
 
 
-def _edgeconv_factored_backward(lib, x, wst, idx, ga, be, ab, mean, invstd, arg, g, need_dx=True):
+def _edgeconv_factored_backward(x, wst, idx, ga, be, ab, mean, invstd, arg, g, need_dx=True):
     """-> dx [P*M, C] | None, dwst [2 cout, C], dgamma, dbeta: the three HIP passes of sapcu_fd_edgeconv_backward, then ONE
-    point-level weight gradient and ONE point-level GEMM.  The caller holds torch.cuda.device(x.device)."""
+    point-level weight gradient and ONE point-level GEMM."""
     P, M, kk = idx.shape
     rows, cin = x.shape
     cout, dev = wst.shape[0] // 2, x.device
     gab = torch.empty_like(ab)
     dgamma, dbeta = torch.empty_like(ga), torch.empty_like(be)
     bad = torch.empty((1,), dtype=torch.int32, device=dev)
-    nbytes = int(lib.sapcu_fd_edgeconv_backward_workspace_bytes(P, M, kk, cout))
-    ws = torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev)
-    st = _lib.current_stream()
-    _lib.check(lib.sapcu_fd_edgeconv_backward(_lib.ptr(ab), _lib.ptr(idx), _lib.ptr(g), _lib.ptr(arg), P, M, kk, cout, _lib.ptr(mean),
-                                              _lib.ptr(invstd), _lib.ptr(ga), _lib.ptr(be), _lib.ptr(gab), _lib.ptr(dgamma), _lib.ptr(dbeta),
-                                              _lib.ptr(bad), _lib.ptr(ws), nbytes, st))
-    _count_bad(bad)
+    ws, nbytes = T._empty_ws("sapcu_fd_edgeconv_backward_workspace_bytes", (P, M, kk, cout), dev)
+    _lib.call("sapcu_fd_edgeconv_backward", dev, ab, idx, g, arg, P, M, kk, cout, mean, invstd, ga, be, gab, dgamma, dbeta, bad, ws, nbytes)
+    bad_index_counter(dev).add_(bad)
     dwst = torch.empty_like(wst)
-    tws, tbytes = T._ws(lib, rows, 2 * cout, cin, dev)
-    T._wgrad(lib, gab, x, rows, 2 * cout, cin, dwst, None, tws, tbytes, st)
+    tws, tbytes = T._empty_ws("sapcu_train_workspace_bytes", (rows, 2 * cout, cin), dev)
+    T._wgrad(gab, x, rows, 2 * cout, cin, dwst, None, tws, tbytes)
     dx = None
     if need_dx:
         dx = torch.empty_like(x)
-        T._gemm(lib, gab, wst.t().contiguous(), None, dx)            # dx[r, c] = gab[r, n] . (Wst^T)[c, n]^T
+        T._gemm(gab, wst.t().contiguous(), None, dx)                 # dx[r, c] = gab[r, n] . (Wst^T)[c, n]^T
     return dx, dwst, dgamma, dbeta
 
 
@@ -356,7 +320,6 @@ class _EdgeConvFactored(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, idx, weight, gamma, beta, eps, running, reps):
         _need_cuda(x, "edgeconv_factored")
-        lib = _lib.load()
         P, M, kk = idx.shape
         _check_patch_shape(M, kk)
         x = x.contiguous()
@@ -372,8 +335,7 @@ class _EdgeConvFactored(torch.autograd.Function):
         wst = torch.cat([w[:, :C], w[:, C:]], dim=0).contiguous()         # W1 and W2 are rounded (bf16 mode) separately
         idx = idx.to(torch.int32).contiguous()
         ga, be = gamma.detach().contiguous(), beta.detach().contiguous()
-        with torch.cuda.device(x.device):
-            ab, mean, var, invstd, out, arg = _edgeconv_factored_forward(lib, x, wst, idx, ga, be, eps)
+        ab, mean, var, invstd, out, arg = _edgeconv_factored_forward(x, wst, idx, ga, be, eps)
         _update_running(running, mean, var, rows * kk, int(reps))
         ctx.save_for_backward(x, wst, ga, be, ab, mean, invstd, arg)
         ctx.idx, ctx.wshape = idx, weight.shape
@@ -381,12 +343,10 @@ class _EdgeConvFactored(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
         x, wst, ga, be, ab, mean, invstd, arg = ctx.saved_tensors
         cout = wst.shape[0] // 2
-        with torch.cuda.device(x.device):
-            dx, dwst, dgamma, dbeta = _edgeconv_factored_backward(lib, x, wst, ctx.idx, ga, be, ab, mean, invstd, arg, g.contiguous(),
-                                                                  ctx.needs_input_grad[0])
+        dx, dwst, dgamma, dbeta = _edgeconv_factored_backward(x, wst, ctx.idx, ga, be, ab, mean, invstd, arg, g.contiguous(),
+                                                              ctx.needs_input_grad[0])
         dw = torch.cat([dwst[:cout], dwst[cout:]], dim=1).reshape(ctx.wshape)
         return dx, None, dw, dgamma, dbeta, None, None, None
 
@@ -403,12 +363,10 @@ def feature_knn(x, P, M, k):
     """The library's free-running neighbour rule on features x [P*M, C]: ``sapcu_patch_knn`` — the k highest scores
     -|x_i - x_j|^2 in descending order, equal scores by ascending index -> int32 [P, M, k]."""
     _need_cuda(x, "feature_knn")
-    lib = _lib.load()
     x = x.contiguous()
     c = x.shape[1]
     idx = torch.empty((P, M, k), dtype=torch.int32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.sapcu_patch_knn(_lib.ptr(x), P, M, c, c, k, _lib.ptr(idx), _lib.current_stream()))
+    _lib.call("sapcu_patch_knn", x.device, x, P, M, c, c, k, idx)
     return idx
 
 

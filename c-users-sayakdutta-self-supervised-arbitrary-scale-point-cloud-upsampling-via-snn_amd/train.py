@@ -17,35 +17,27 @@ class _LifSelfLoopTrain(torch.autograd.Function):
     def forward(ctx, x, membrane_decay, threshold_adapt, refractory_decay, threshold_base, steps):
         if not x.is_cuda or x.dtype != torch.float32:
             raise ValueError("lif_selfloop_train: expected a CUDA float32 tensor (there is no CPU path)")
-        lib = _lib.load()
         shape = x.shape
         ch = shape[1]
         x2 = x.movedim(1, -1).contiguous()                      # channels last: [rows, C]
         rows = x2.numel() // ch
         params = [p.detach().contiguous() for p in (membrane_decay, threshold_adapt, refractory_decay, threshold_base)]
         out = torch.empty_like(x2)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sapcu_lif_train_forward(_lib.ptr(x2), rows, ch, int(steps), *[_lib.ptr(p) for p in params],
-                                                   _lib.ptr(out), _lib.current_stream()))
+        _lib.call("sapcu_lif_train_forward", x.device, x2, rows, ch, int(steps), *params, out)
         ctx.save_for_backward(x2, *params)
         ctx.steps, ctx.shape = int(steps), shape
         return out.movedim(-1, 1)
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x2, md, ta, rd, tb = ctx.saved_tensors
         ch = x2.shape[-1]
         rows = x2.numel() // ch
         g2 = grad_out.movedim(1, -1).contiguous()
         gx = torch.empty_like(x2)
         gp = [torch.empty_like(md) for _ in range(4)]
-        nbytes = int(lib.sapcu_lif_train_workspace_bytes(rows, ch))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x2.device)
-        with torch.cuda.device(x2.device):
-            _lib.check(lib.sapcu_lif_train_backward(_lib.ptr(x2), _lib.ptr(g2), rows, ch, ctx.steps, _lib.ptr(md), _lib.ptr(ta),
-                                                    _lib.ptr(rd), _lib.ptr(tb), _lib.ptr(gx), *[_lib.ptr(g) for g in gp],
-                                                    _lib.ptr(ws), nbytes, _lib.current_stream()))
+        ws, nbytes = _empty_ws("sapcu_lif_train_workspace_bytes", (rows, ch), x2.device)
+        _lib.call("sapcu_lif_train_backward", x2.device, x2, g2, rows, ch, ctx.steps, md, ta, rd, tb, gx, *gp, ws, nbytes)
         return (gx.movedim(-1, 1), gp[0], gp[1], gp[2], gp[3], None)
 
 
@@ -55,9 +47,12 @@ def lif_selfloop_train(x, membrane_decay, threshold_adapt, refractory_decay, thr
     return _LifSelfLoopTrain.apply(x, membrane_decay, threshold_adapt, refractory_decay, threshold_base, steps)
 
 
-def _ws(lib, rows, ch, k, dev):
-    nbytes = int(lib.sapcu_train_workspace_bytes(rows, ch, k))
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+def _empty_ws(sizer, sizes, dev):
+    """(workspace, nbytes) for one call: what the sizer ``sizer`` returns for the integer arguments ``sizes``, UNINITIALISED — every
+    entry point writes what it reads of its workspace, and a memset per op would be one more node of a captured training step.  A
+    sizer's refusal (negative) is passed on with an empty tensor: the entry point refuses the same shape with its own message."""
+    nbytes = int(getattr(_lib.load(), sizer)(*sizes))
+    return torch.empty((max(nbytes, 0),), dtype=torch.uint8, device=dev), nbytes
 
 
 # Arithmetic of the training GEMMs (forward, data gradient, weight gradient): "f32" = the exact-f32 MFMA kernels (the parity
@@ -85,37 +80,32 @@ class gemm_precision(object):
         return False
 
 
-def _gemm(lib, a, w, bias, out):
+def _gemm(a, w, bias, out):
     """out[r, n] = a[r, k] . w[n, k]^T (+ bias): the exact-f32 MFMA kernel (k % 32 == 0), or bf16 operands."""
     r, k = a.shape
     n = w.shape[0]
     if _GEMM_PRECISION[0] == "bf16":
-        _lib.check(lib.sapcu_gemm_bf16(_lib.ptr(a), r, k, k, _lib.ptr(w), n, _lib.ptr(bias), _lib.ptr(out), n, _lib.current_stream()))
-        return out
-    _lib.check(lib.sapcu_gemm_f32(_lib.ptr(a), r, k, k, _lib.ptr(w), n, _lib.ptr(bias), None, 0, _lib.ptr(out), n, None, 0, 0,
-                                  _lib.current_stream()))
+        _lib.call("sapcu_gemm_bf16", a.device, a, r, k, k, w, n, bias, out, n)
+    else:
+        _lib.call("sapcu_gemm_f32", a.device, a, r, k, k, w, n, bias, None, 0, out, n, None, 0, 0)
     return out
 
 
-def _wgrad(lib, dy, x, rows, cout, cin, dw, db, ws, nbytes, st):
-    """dw[cout, cin] = dy^T . x, db = column sums of dy — f32 or bf16 operands like _gemm."""
+def _wgrad(dy, x, rows, cout, cin, dw, db, ws, nbytes):
+    """dw[cout, cin] = dy^T . x, db = column sums of dy — f32 or bf16 operands like _gemm.  ws: the caller's
+    sapcu_train_workspace_bytes(rows, cout, cin) workspace, used when it holds what the bf16 kernel asks for as well."""
+    entry = "sapcu_conv1x1_wgrad_f32"
     if _GEMM_PRECISION[0] == "bf16":
-        need = int(lib.sapcu_wgrad_bf16_workspace_bytes(rows, cout, cin))
-        if need > nbytes:
-            ws = torch.empty((need,), dtype=torch.uint8, device=dy.device)
-            nbytes = need
-        _lib.check(lib.sapcu_conv1x1_wgrad_bf16(_lib.ptr(dy), cout, _lib.ptr(x), cin, rows, cout, cin, _lib.ptr(dw), _lib.ptr(db),
-                                                _lib.ptr(ws), nbytes, st))
-        return
-    _lib.check(lib.sapcu_conv1x1_wgrad_f32(_lib.ptr(dy), cout, _lib.ptr(x), cin, rows, cout, cin, _lib.ptr(dw), _lib.ptr(db),
-                                           _lib.ptr(ws), nbytes, st))
+        entry = "sapcu_conv1x1_wgrad_bf16"
+        if int(_lib.load().sapcu_wgrad_bf16_workspace_bytes(rows, cout, cin)) > nbytes:
+            ws, nbytes = _empty_ws("sapcu_wgrad_bf16_workspace_bytes", (rows, cout, cin), dy.device)
+    _lib.call(entry, dy.device, dy, cout, x, cin, rows, cout, cin, dw, db, ws, nbytes)
 
 
 class _ConvBnLifTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, membrane_decay, threshold_adapt, refractory_decay, threshold_base, steps, eps,
                 running=None):
-        lib = _lib.load()
         rows, cin = x.shape
         cout = weight.shape[0]
         if cin % 32 or cout % 32:
@@ -127,17 +117,14 @@ class _ConvBnLifTrain(torch.autograd.Function):
         y = torch.empty((rows, cout), dtype=torch.float32, device=dev)
         z = torch.empty_like(y)
         mean, var, invstd = (torch.empty((cout,), dtype=torch.float32, device=dev) for _ in range(3))
-        ws, nbytes = _ws(lib, rows, cout, 0, dev)
-        with torch.cuda.device(dev):
-            _gemm(lib, x, w, bias.detach().contiguous(), y)
-            _lib.check(lib.sapcu_bn_train_forward(_lib.ptr(y), rows, cout, _lib.ptr(gamma.detach().contiguous()),
-                                                  _lib.ptr(beta.detach().contiguous()), float(eps), _lib.ptr(z), _lib.ptr(mean),
-                                                  _lib.ptr(var), _lib.ptr(invstd), _lib.ptr(ws), nbytes, _lib.current_stream()))
-            out = z
-            if int(steps) > 0:
-                out = torch.empty_like(y)
-                _lib.check(lib.sapcu_lif_train_forward(_lib.ptr(z), rows, cout, int(steps), *[_lib.ptr(p) for p in prm],
-                                                       _lib.ptr(out), _lib.current_stream()))
+        ws, nbytes = _empty_ws("sapcu_train_workspace_bytes", (rows, cout, 0), dev)
+        _gemm(x, w, bias.detach().contiguous(), y)
+        _lib.call("sapcu_bn_train_forward", dev, y, rows, cout, gamma.detach().contiguous(), beta.detach().contiguous(), float(eps), z,
+                  mean, var, invstd, ws, nbytes)
+        out = z
+        if int(steps) > 0:
+            out = torch.empty_like(y)
+            _lib.call("sapcu_lif_train_forward", dev, z, rows, cout, int(steps), *prm, out)
         if running is not None:                     # nn.BatchNorm's train()-mode bookkeeping: momentum update, unbiased variance
             r_mean, r_var, n_tracked, momentum = running
             if rows < 2:
@@ -153,7 +140,6 @@ class _ConvBnLifTrain(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, w, gamma, y, z, mean, invstd, *nrn = ctx.saved_tensors
         rows, cin = x.shape
         cout = w.shape[0]
@@ -163,27 +149,20 @@ class _ConvBnLifTrain(torch.autograd.Function):
         gp = [None] * 4                                   # no neuron (steps == 0): the four parameter slots are placeholders
         dgamma, dbeta, dbias = (torch.empty((cout,), dtype=torch.float32, device=dev) for _ in range(3))
         dw = torch.empty_like(w)
-        ws, nbytes = _ws(lib, rows, cout, cin, dev)
-        with torch.cuda.device(dev):
-            st = _lib.current_stream()
-            if ctx.steps > 0:
-                md, ta, rd, tb = nrn
-                gp = [torch.empty_like(md) for _ in range(4)]
-                lws_bytes = int(lib.sapcu_lif_train_workspace_bytes(rows, cout))
-                lws = torch.empty((lws_bytes,), dtype=torch.uint8, device=dev)
-                _lib.check(lib.sapcu_lif_train_backward(_lib.ptr(z), _lib.ptr(g), rows, cout, ctx.steps, _lib.ptr(md), _lib.ptr(ta),
-                                                        _lib.ptr(rd), _lib.ptr(tb), _lib.ptr(dz), *[_lib.ptr(t) for t in gp],
-                                                        _lib.ptr(lws), lws_bytes, st))
-            else:
-                dz = g
-            _lib.check(lib.sapcu_bn_train_backward(_lib.ptr(y), _lib.ptr(dz), rows, cout, _lib.ptr(gamma), _lib.ptr(mean),
-                                                   _lib.ptr(invstd), _lib.ptr(dy), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws),
-                                                   nbytes, st))
-            _wgrad(lib, dy, x, rows, cout, cin, dw, dbias, ws, nbytes, st)
-            if ctx.needs_input_grad[0]:
-                _gemm(lib, dy, w.t().contiguous(), None, dx)        # dx[r, cin] = dy[r, cout] . (W^T)[cin, cout]^T
-            else:
-                dx = None
+        ws, nbytes = _empty_ws("sapcu_train_workspace_bytes", (rows, cout, cin), dev)
+        if ctx.steps > 0:
+            md, ta, rd, tb = nrn
+            gp = [torch.empty_like(md) for _ in range(4)]
+            lws, lws_bytes = _empty_ws("sapcu_lif_train_workspace_bytes", (rows, cout), dev)
+            _lib.call("sapcu_lif_train_backward", dev, z, g, rows, cout, ctx.steps, md, ta, rd, tb, dz, *gp, lws, lws_bytes)
+        else:
+            dz = g
+        _lib.call("sapcu_bn_train_backward", dev, y, dz, rows, cout, gamma, mean, invstd, dy, dgamma, dbeta, ws, nbytes)
+        _wgrad(dy, x, rows, cout, cin, dw, dbias, ws, nbytes)
+        if ctx.needs_input_grad[0]:
+            _gemm(dy, w.t().contiguous(), None, dx)             # dx[r, cin] = dy[r, cout] . (W^T)[cin, cout]^T
+        else:
+            dx = None
         return (dx, dw, dbias, dgamma, dbeta, gp[0], gp[1], gp[2], gp[3], None, None, None)
 
 
@@ -201,17 +180,13 @@ def conv_bn_lif_train(x, weight, bias, gamma, beta, membrane_decay, threshold_ad
 class _SoftmaxAgg(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, pe, v, idx, m, sqrt_hd, keep):
-        lib = _lib.load()
         pts, d = v.shape
         kk = a.shape[0] // pts
         a, pe, v = a.contiguous(), pe.contiguous(), v.contiguous()
         idx = idx.contiguous().to(torch.int32)
         keep = keep.contiguous() if keep is not None else None
         res = torch.empty((pts, d), dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            _lib.check(lib.sapcu_softmax_agg_forward(_lib.ptr(a), _lib.ptr(pe), _lib.ptr(v), d, _lib.ptr(idx),
-                                                     _lib.ptr(keep) if keep is not None else None, pts, int(m), kk, d,
-                                                     float(sqrt_hd), _lib.ptr(res), _lib.current_stream()))
+        _lib.call("sapcu_softmax_agg_forward", a.device, a, pe, v, d, idx, keep, pts, int(m), kk, d, float(sqrt_hd), res)
         ctx.save_for_backward(a, pe, v, idx)
         ctx.keep = keep
         ctx.m, ctx.sqrt_hd = int(m), float(sqrt_hd)
@@ -219,16 +194,12 @@ class _SoftmaxAgg(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_res):
-        lib = _lib.load()
         a, pe, v, idx = ctx.saved_tensors
         pts, d = v.shape
         kk = a.shape[0] // pts
         ga, gpe, gv = torch.empty_like(a), torch.empty_like(pe), torch.empty_like(v)
-        with torch.cuda.device(a.device):
-            _lib.check(lib.sapcu_softmax_agg_backward(_lib.ptr(a), _lib.ptr(pe), _lib.ptr(v), d, _lib.ptr(idx),
-                                                      _lib.ptr(ctx.keep) if ctx.keep is not None else None,
-                                                      _lib.ptr(grad_res.contiguous()), pts, ctx.m, kk, d, ctx.sqrt_hd, _lib.ptr(ga),
-                                                      _lib.ptr(gpe), _lib.ptr(gv), d, _lib.current_stream()))
+        _lib.call("sapcu_softmax_agg_backward", a.device, a, pe, v, d, idx, ctx.keep, grad_res.contiguous(), pts, ctx.m, kk, d, ctx.sqrt_hd,
+                  ga, gpe, gv, d)
         return ga, gpe, gv, None, None, None, None
 
 
@@ -280,13 +251,11 @@ def conv_bn_train(x, weight, bias, gamma, beta, eps=1e-5, running=None):
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, index, group=None):
-        lib = _lib.load()
         src = src.contiguous()
         index = index.contiguous().to(torch.int64)
         rows, d = index.shape[0], src.shape[1]
         out = torch.empty((rows, d), dtype=torch.float32, device=src.device)
-        with torch.cuda.device(src.device):
-            _lib.check(lib.sapcu_gather_rows(_lib.ptr(src), d, _lib.ptr(index), rows, d, _lib.ptr(out), _lib.current_stream()))
+        _lib.call("sapcu_gather_rows", src.device, src, d, index, rows, d, out)
         ctx.save_for_backward(index)
         ctx.src_rows = src.shape[0]
         ctx.group = group
@@ -294,19 +263,15 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         (index,) = ctx.saved_tensors
         g = grad_out.contiguous()
         rows, d = g.shape
         gsrc = torch.empty((ctx.src_rows, d), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            if ctx.group is not None:           # patch-structured index: the deterministic segmented sum
-                gs, gr = ctx.group
-                _lib.check(lib.sapcu_scatter_add_rows_grouped(_lib.ptr(g), _lib.ptr(index), rows, d, _lib.ptr(gsrc), d, ctx.src_rows,
-                                                              int(gs), int(gr), None, _lib.current_stream()))
-            else:                               # arbitrary index: float atomics (summation order not fixed)
-                _lib.check(lib.sapcu_scatter_add_rows(_lib.ptr(g), _lib.ptr(index), rows, d, _lib.ptr(gsrc), d, ctx.src_rows,
-                                                      _lib.current_stream()))
+        if ctx.group is not None:               # patch-structured index: the deterministic segmented sum
+            gs, gr = ctx.group
+            _lib.call("sapcu_scatter_add_rows_grouped", g.device, g, index, rows, d, gsrc, d, ctx.src_rows, int(gs), int(gr), None)
+        else:                                   # arbitrary index: float atomics (summation order not fixed)
+            _lib.call("sapcu_scatter_add_rows", g.device, g, index, rows, d, gsrc, d, ctx.src_rows)
         return gsrc, None, None
 
 
@@ -384,26 +349,22 @@ def transformer_block_train(p, xyz, features, knn_idx, time_steps=4, num_heads=8
 class _LinearTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
-        lib = _lib.load()
         x, w = x.contiguous(), weight.detach().contiguous()
         out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _gemm(lib, x, w, bias.detach().contiguous(), out)
+        _gemm(x, w, bias.detach().contiguous(), out)
         ctx.save_for_backward(x, w)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, w = ctx.saved_tensors
         rows, cin = x.shape
         cout = w.shape[0]
         g = grad_out.contiguous()
         dw, db, dx = torch.empty_like(w), torch.empty((cout,), dtype=torch.float32, device=x.device), torch.empty_like(x)
-        ws, nbytes = _ws(lib, rows, cout, cin, x.device)
-        with torch.cuda.device(x.device):
-            _wgrad(lib, g, x, rows, cout, cin, dw, db, ws, nbytes, _lib.current_stream())
-            _gemm(lib, g, w.t().contiguous(), None, dx)
+        ws, nbytes = _empty_ws("sapcu_train_workspace_bytes", (rows, cout, cin), x.device)
+        _wgrad(g, x, rows, cout, cin, dw, db, ws, nbytes)
+        _gemm(g, w.t().contiguous(), None, dx)
         return dx, dw, db
 
 
@@ -422,27 +383,22 @@ def linear_train(x, weight, bias):
 class _GroupMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, m):
-        lib = _lib.load()
         x = x.contiguous()
         c = x.shape[1]
         groups = x.shape[0] // m
         out = torch.empty((groups, c), dtype=torch.float32, device=x.device)
         arg = torch.empty((groups, c), dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.sapcu_group_max_forward(_lib.ptr(x), groups, int(m), c, _lib.ptr(out), _lib.ptr(arg), _lib.current_stream()))
+        _lib.call("sapcu_group_max_forward", x.device, x, groups, int(m), c, out, arg)
         ctx.save_for_backward(arg)
         ctx.m = int(m)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         (arg,) = ctx.saved_tensors
         groups, c = arg.shape
         gx = torch.empty((groups * ctx.m, c), dtype=torch.float32, device=arg.device)
-        with torch.cuda.device(arg.device):
-            _lib.check(lib.sapcu_group_max_backward(_lib.ptr(grad_out.contiguous()), _lib.ptr(arg), groups, ctx.m, c, _lib.ptr(gx),
-                                                    _lib.current_stream()))
+        _lib.call("sapcu_group_max_backward", arg.device, grad_out.contiguous(), arg, groups, ctx.m, c, gx)
         return gx, None
 
 
@@ -453,12 +409,10 @@ def group_max(x, m):
 
 def inpatch_knn(xyz, k):
     """In-patch kNN of fn's blocks (fn/snn_coder.py:31-39) on the device: xyz [B, N, 3] -> int32 [B, N, k]."""
-    lib = _lib.load()
     B, N, _ = xyz.shape
     x = xyz.contiguous()
     idx = torch.empty((B, N, k), dtype=torch.int32, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        _lib.check(lib.sapcu_patch_knn(_lib.ptr(x), B, N, 3, 3, k, _lib.ptr(idx), _lib.current_stream()))
+    _lib.call("sapcu_patch_knn", xyz.device, x, B, N, 3, 3, k, idx)
     return idx
 
 

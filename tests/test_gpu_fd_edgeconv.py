@@ -91,9 +91,9 @@ def test_smallest_case_one_edge_row_equals_the_feature_ops(mode):
             op()
     wst = torch.cat([w[:, :C], w[:, C:]], dim=0).contiguous()
     with T.gemm_precision(mode):
-        ab, mean, var, invstd, out, arg = fd_train._edgeconv_factored_forward(lib, x, wst, idx, gamma, beta, 1e-5)
+        ab, mean, var, invstd, out, arg = fd_train._edgeconv_factored_forward(x, wst, idx, gamma, beta, 1e-5)
         y = torch.empty(1, cout, device=U.dev())
-        T._gemm(lib, fd_train.edge_feature_forward(x, idx), w, None, y)
+        T._gemm(fd_train.edge_feature_forward(x, idx), w, None, y)
         st = [torch.empty(cout, device=U.dev()) for _ in range(3)]
         need = int(lib.sapcu_fd_bn_stats_workspace_bytes(1, cout))
         ws = torch.empty(need, dtype=torch.uint8, device=U.dev())
@@ -104,7 +104,7 @@ def test_smallest_case_one_edge_row_equals_the_feature_ops(mode):
         for name, a, b in zip(("out", "arg", "mean", "var", "invstd"), (out, arg, mean, var, invstd), (o2, a2, st[0], st[1], st[2])):
             assert torch.equal(a, b), name
         assert not bool(var.any()) and not bool(arg.any())
-        g = [fd_train._edgeconv_factored_backward(lib, x, wst, idx, gamma, beta, ab, mean, invstd, arg, go) for _ in range(2)]
+        g = [fd_train._edgeconv_factored_backward(x, wst, idx, gamma, beta, ab, mean, invstd, arg, go) for _ in range(2)]
     assert fd_train.take_bad_index_count() == 0
     for a, b in zip(*g):
         assert torch.equal(a, b) and bool(torch.isfinite(a).all())
