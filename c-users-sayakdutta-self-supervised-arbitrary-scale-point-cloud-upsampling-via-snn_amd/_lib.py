@@ -216,6 +216,9 @@ TABLES[None] = _INTERNAL_SIGNATURES = {
     "sapcu_internal_geodesic_disks_limited": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                                       c_int64, POINTER(c_double), c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                                                       c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+    # sapcu_poisson_select_f32 (csrc/sapcu_poisson.h) on the grid path at any C, one round per chunk: tests/test_gpu_poisson.py
+    "sapcu_internal_poisson_select_grid": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                   c_void_p]),
 }
 # csrc/sapcu_geodesic.h: geodesic disks on a mesh, the counts behind the uniformity figure (sapcu_amd/uniformity.py).  radii_host is a
 # HOST double[nr], info_host a HOST int64[8].  Bound by load() like a table; kept beside TABLES because tests/abi_tables.py holds
@@ -227,6 +230,15 @@ GEODESIC_SIGNATURES = {
                                          c_void_p]),
 }
 GEODESIC_EXPORTS = tuple(GEODESIC_SIGNATURES)
+# csrc/sapcu_poisson.h: Poisson-disk selection and the exact-count subsample of a cloud (sapcu_amd/poisson.py); every pointer is a
+# DEVICE array.  Beside TABLES for the reason GEODESIC_SIGNATURES is
+POISSON_SIGNATURES = {
+    "sapcu_poisson_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "sapcu_poisson_select_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sapcu_poisson_subsample_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int64, c_void_p]),
+}
+POISSON_EXPORTS = tuple(POISSON_SIGNATURES)
 _lib = None
 
 
@@ -244,7 +256,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in ((name, sig) for table in list(TABLES.values()) + [GEODESIC_SIGNATURES] for name, sig in table.items()):
+    for name, (res, args) in ((name, sig) for table in list(TABLES.values()) + [GEODESIC_SIGNATURES, POISSON_SIGNATURES] for name, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -11,7 +11,8 @@ augmentation draws every output equals the reference's bit for bit, up to its BL
 ``train_step.run_epoch(trainer, loader)`` for ``fd_trainer`` / ``fn_trainer``.  The draws (angle, scale, jitter, centres, order) come
 from a device ``torch.Generator`` seeded by (seed, epoch, batch): deterministic, and not the reference's numpy stream.
 ``FdRayPatches`` yields fd's ray samples of one mesh per item (the reference's ``scripts/sample_mesh-rd.py`` -> ``fd.npz``), sampled
-and cast afresh on the device (``ray.sample_fd_rays``).
+and cast afresh on the device (``ray.sample_fd_rays``).  ``PoissonPU1KPatches`` yields ``PU1KPatches``'s batches from
+meshes: both clouds of a sample are Poisson-disk sampled afresh on the device (``poisson.poisson_disk_sample``).
 
 No CPU path: the HIP library and a device are required.
 """
@@ -22,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import _inputs, _lib, mesh as mesh_mod, ray as ray_mod, surface
+from . import _inputs, _lib, mesh as mesh_mod, poisson as poisson_mod, ray as ray_mod, surface
 
 MAX_N, MAX_G, MAX_K = 4096, 65536, 128
 
@@ -290,6 +291,20 @@ def mesh_files(folder):
     return sorted(files)
 
 
+def _split_meshes(meshes, configure):
+    """(names, pairs) of a split's meshes: ``meshes`` is a list of (vertices, faces) or a folder of ``.off`` files (``mesh_files``;
+    polygons are fan-triangulated, vertices taken as f32), ``configure(total)`` gives the split's range [lo, hi)."""
+    if isinstance(meshes, (str, os.PathLike)):
+        files = mesh_files(meshes)
+        lo, hi = configure(len(files))
+        names = files[lo:hi]
+        pairs = [mesh_mod.read_off(f, triangulate=True) for f in names]
+        return names, [(v.astype(np.float32), f) for v, f in pairs]
+    meshes = list(meshes)
+    lo, hi = configure(len(meshes))
+    return ["mesh %d" % i for i in range(lo, hi)], meshes[lo:hi]
+
+
 class MeshSurfacePatches(MeshPatches):
     """The stacked batches of the reference's ``PU1KMeshDataset`` (fn/datacore.py) from the meshes themselves: every batch draws a NEW
     area-weighted sampling of ``num_points`` surface points with their face normals per mesh (``surface.sample_surface``: one launch),
@@ -305,21 +320,8 @@ class MeshSurfacePatches(MeshPatches):
                  seed=0, device=None, drop_last=False):
         if int(num_patches) < 1:
             raise ValueError("num_patches must be >= 1")
-        files = None
-        if isinstance(meshes, (str, os.PathLike)):
-            files = mesh_files(meshes)
-            total = len(files)
-        else:
-            meshes = list(meshes)
-            total = len(meshes)
-        lo, hi = self._configure(total, int(num_points), "num_points", split, k_neighbors, batch_size, shuffle, augment, seed, device,
-                                 drop_last)
-        if files is not None:
-            names = files[lo:hi]
-            pairs = [mesh_mod.read_off(f, triangulate=True) for f in names]
-            pairs = [(v.astype(np.float32), f) for v, f in pairs]
-        else:
-            names, pairs = ["mesh %d" % i for i in range(lo, hi)], meshes[lo:hi]
+        names, pairs = _split_meshes(meshes, lambda total: self._configure(total, int(num_points), "num_points", split, k_neighbors, batch_size,
+                                                                          shuffle, augment, seed, device, drop_last))
         self.num_patches = int(num_patches)
         self.tables = surface.build_surface_tables(pairs, device=self.device, names=names)
 
@@ -331,6 +333,53 @@ class MeshSurfacePatches(MeshPatches):
         points, normals, faces = surface.sample_surface(self.tables, idx, n, u, r1, r2, validate=False)
         rows = torch.arange(b, dtype=torch.int64, device=dev)
         return self._patches(points, normals, rows, idx, gen, {"u": u, "r1": r1, "r2": r2, "faces": faces})
+
+
+class PoissonPU1KPatches(_DeviceLoader):
+    """``PU1KPatches``'s batches — the data set fd/config.py selects — made from the meshes themselves: per batch entry a NEW
+    Poisson-disk cloud of ``num_input`` points and, independently, one of ``num_dense`` points of the same mesh
+    (``poisson.poisson_disk_sample``: ``oversample`` times as many area-weighted candidates, thinned to the exact count), then
+    ``build_patches`` on the pair; the returned dict is ``PU1KPatches``'s (``input``, ``len``, ``cloud``, ``points``, ``index``).
+    ``meshes``: a list of (vertices, faces) or a folder of ``.off`` files, handled and split as ``MeshSurfacePatches`` does, the
+    sampling tables built once.
+
+    What differs from the reference's h5 files: these clouds cover WHOLE meshes, not the patches PU-GAN cut from its meshes before
+    sampling them, and the random streams are the device generator's, not those of the tool that wrote the files.  Per batch all
+    draws come from the (seed, epoch, batch) generator: ``u`` (f64), ``r1``, ``r2`` (f64 rounded to f32) [b, oversample *
+    num_input] of the input cloud, then the same for the dense cloud, then the augmentation's.  ``last_draws`` holds them
+    (``u_input`` .. ``r2_dense``), with ``radius_*``, ``count_*`` and ``idx_*`` of both selections."""
+
+    STEPS = 20
+
+    def __init__(self, meshes, num_input=256, num_dense=1024, oversample=8, k_neighbors=32, split="train", batch_size=4, shuffle=True,
+                 augment=None, seed=0, device=None, drop_last=False):
+        if not 1 <= int(num_dense) <= MAX_G:
+            raise ValueError("num_dense: need 1 <= num_dense <= %d points" % MAX_G)
+        if int(oversample) < 1:
+            raise ValueError("oversample must be >= 1")
+        names, pairs = _split_meshes(meshes, lambda total: self._configure(total, int(num_input), "num_input", split, k_neighbors, batch_size,
+                                                                          shuffle, augment, seed, device, drop_last))
+        self.num_dense, self.oversample = int(num_dense), int(oversample)
+        self.tables = surface.build_surface_tables(pairs, device=self.device, names=names)
+
+    def _cloud(self, idx, n, gen, tag, draws):
+        b, C, dev = idx.shape[0], self.oversample * n, self.device
+        u = torch.rand((b, C), generator=gen, device=dev, dtype=torch.float64)
+        r1 = torch.rand((b, C), generator=gen, device=dev, dtype=torch.float64).float()
+        r2 = torch.rand((b, C), generator=gen, device=dev, dtype=torch.float64).float()
+        points, _, _, radius, count, kept = poisson_mod.poisson_disk_sample(self.tables, idx, n, u, r1, r2, steps=self.STEPS, validate=False)
+        draws.update({"u_" + tag: u, "r1_" + tag: r1, "r2_" + tag: r2, "radius_" + tag: radius, "count_" + tag: count, "idx_" + tag: kept})
+        return points
+
+    def _batch(self, idx, gen):
+        draws = {}
+        inputs = self._cloud(idx, self._n, gen, "input", draws)
+        dense = self._cloud(idx, self.num_dense, gen, "dense", draws)
+        rot, scale, jitter, theta = self._draws(gen, idx.shape[0])
+        self.last_draws = dict(draws, theta=theta, rotation=rot, scale=scale, jitter=jitter)
+        rows = torch.arange(idx.shape[0], dtype=torch.int64, device=self.device)
+        o = build_patches(inputs, rows, self.k_neighbors, dense=dense, rotation=rot, scale=scale, jitter=jitter, validate=False)
+        return {"input": o["patches"], "len": o["len"], "cloud": o["cloud"], "points": o["dense"], "index": idx}
 
 
 class FdRayPatches(object):
