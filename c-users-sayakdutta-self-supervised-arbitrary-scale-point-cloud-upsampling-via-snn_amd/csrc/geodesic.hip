@@ -22,6 +22,7 @@
 //   The loop ends on "queue empty", on the window cap and on a queue past the workspace ring (header).
 #include "common.h"
 #include "sapcu_geodesic.h"
+#include "wave_ops.h"
 
 namespace sapcu {
 
@@ -221,20 +222,13 @@ __global__ __launch_bounds__(256) void geo_target_count_kernel(GeoWs w, const in
 
 // exclusive scan of the counts in fstart[1 .. nf] in place (fstart[0] = 0), one work group; fcur = the starts
 __global__ __launch_bounds__(1024) void geo_scan_kernel(GeoWs w, int nf) {
-    __shared__ int part[1024];
+    __shared__ int scr[16];
     const int tid = threadIdx.x, chunk = (nf + 1023) / 1024;
     const int a = min(nf, tid * chunk), b = min(nf, a + chunk);
     int s = 0;
     for (int i = a; i < b; ++i) s += w.fstart[i + 1];
-    part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int add = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    int run = part[tid] - s;                                        // targets of the faces before a
+    int total;
+    int run = block_excl_scan<16>(s, scr, &total);                  // targets of the faces before a
     for (int i = a; i < b; ++i) {
         const int c = w.fstart[i + 1];
         w.fcur[i] = run;

@@ -4,6 +4,7 @@
 // (grid_partials_fold).  Kernels live in knn_grid.hip; a kernel is launched from the file that defines it.
 #pragma once
 #include "common.h"
+#include "wave_ops.h"
 
 namespace sapcu {
 
@@ -154,13 +155,8 @@ __device__ __forceinline__ void grid_partials_fold(const double* __restrict__ pa
         for (int c = 0; c < 6; ++c)
             if (fabs(q[c]) <= 1e150) a = fmax(a, fabs(q[c]));               // a block without points holds +-inf
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a = fmax(a, __shfl_xor(a, o));
-        f = fmax(f, __shfl_xor(f, o));
-    }
-    if (amax) *amax = a;
-    *bad = fmax(*bad, f);
+    if (amax) *amax = wave_max(a);
+    *bad = fmax(*bad, wave_max(f));
 }
 
 int launch_exclusive_scan_int(int* a, int64_t m, int* tile_sums, hipStream_t st);

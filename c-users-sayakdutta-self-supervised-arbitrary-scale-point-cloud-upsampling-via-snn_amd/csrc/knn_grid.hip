@@ -6,22 +6,21 @@
 //     key = (cz*gy + cy)*gx + cx with c = floor((p - origin) / h) clamped to the grid, counting sort (integer atomics
 //     for the counts, a three-kernel exclusive scan, integer atomics for the slots) into a cell-ordered SoA copy
 //     x|y|z plus the original indices.  The order inside a cell is arbitrary: the (distance, index) keys decide;
-//   * one query per wavefront (4 per 256-thread workgroup).  The running top-k is the sorted list of knn_outer.hip,
-//     distributed across the lanes (entry p in lane p, k <= 64); candidates arrive in cell order, not index order, so
+//   * one query per wavefront (4 per 256-thread workgroup).  The running top-k is the keyed WaveTopK of wave_ops.h, a sorted
+//     list spread over the lanes (entry p in lane p, k <= 64); candidates arrive in cell order, not index order, so
 //     a candidate is compared on the key (d, i) — a point at the k-th distance with a lower index still enters;
 //   * the search is grid_shell_walk (knn_grid.h: the shells, the lower bound after each and the stop rule), with GridParams.slack
 //     as the margin, against the current k-th squared distance;
 //   * the squared distance is ((q-p)_x^2 + (q-p)_y^2) + (q-p)_z^2 in separately rounded f64 operations, the output
-//     distance sqrt_cr of it: bit for bit the arithmetic and the order of knn_outer.hip;
+//     distance sqrt_cr of it (dist2_rn): bit for bit the arithmetic and the order of knn_outer.hip;
 //   * non-finite or huge (|x| > 1e150) coordinates, and n < KNN_GRID_MIN_N with the automatic cell size, run the
 //     brute-force kernel of knn_outer.hip instead (the launcher reads the grid parameters back: one stream sync).
 //
 // Statistics (outlier_stats_kernel, outlier_keep_kernel): numpy 2.x np.mean of a C-contiguous f64 [n,kk] table —
-//   * the row mean is the pairwise leaf of kk <= 128 values (8 accumulators over the first kk - kk%8 values, combined
-//     ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the rest added in order; fewer than 8: a plain sum from 0) over kk;
+//   * the row mean is the pairwise leaf of kk <= 128 values (np_leaf_sum, wave_ops.h) over kk;
 //   * the global sum is the flattened table cut into chunks of `bufsize` elements (np.getbufsize()), each summed by
-//     numpy's recursive pairwise sum (split at n/2 rounded down to a multiple of 8, leaves <= 128 as above); the chunk
-//     sums are added in sequence from 0.0 by the caller (sapcu_amd/generation.py), since they may come from several ranks.
+//     numpy's recursive pairwise sum (wave_ops.h: plan, leaves, fold); the chunk sums are added in sequence from 0.0 by
+//     the caller (sapcu_amd/generation.py), since they may come from several ranks.
 #include "common.h"
 #include "knn_grid.h"
 
@@ -41,16 +40,13 @@ __global__ __launch_bounds__(256) void grid_bbox_kernel(const double* __restrict
         hy = fmax(hy, y);
         hz = fmax(hz, z);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lx = fmin(lx, __shfl_xor(lx, o));
-        ly = fmin(ly, __shfl_xor(ly, o));
-        lz = fmin(lz, __shfl_xor(lz, o));
-        hx = fmax(hx, __shfl_xor(hx, o));
-        hy = fmax(hy, __shfl_xor(hy, o));
-        hz = fmax(hz, __shfl_xor(hz, o));
-        bad = fmax(bad, __shfl_xor(bad, o));
-    }
+    lx = wave_min(lx);
+    ly = wave_min(ly);
+    lz = wave_min(lz);
+    hx = wave_max(hx);
+    hy = wave_max(hy);
+    hz = wave_max(hz);
+    bad = wave_max(bad);
     __shared__ double red[4][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
@@ -134,23 +130,6 @@ __global__ __launch_bounds__(256) void grid_count_kernel(const double* __restric
 }
 
 // exclusive scan of the int counts in tiles of SCAN_TILE: per-tile sums, a one-workgroup scan of those, per-tile apply
-__device__ __forceinline__ int block_excl_scan256(int v, int* red4, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) red4[wave] = x;
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += red4[w];
-    *total = red4[0] + red4[1] + red4[2] + red4[3];
-    __syncthreads();
-    return off + x - v;
-}
-
 __global__ __launch_bounds__(256) void scan_tile_sum_kernel(const int* __restrict__ a, int64_t m, int* __restrict__ tile_sums) {
     __shared__ int red4[4];
     const int64_t b = (int64_t)blockIdx.x * SCAN_TILE + threadIdx.x * 4;
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(256) void scan_tile_sum_kernel(const int* __restric
     for (int j = 0; j < 4; ++j)
         if (b + j < m) s += a[b + j];
     int total;
-    block_excl_scan256(s, red4, &total);
+    block_excl_scan<4>(s, red4, &total);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
 }
 
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(256) void scan_tile_offsets_kernel(int* __restrict_
         const int64_t t = base + threadIdx.x;
         const int v = t < tiles ? tile_sums[t] : 0;
         int total;
-        const int ex = block_excl_scan256(v, red4, &total);
+        const int ex = block_excl_scan<4>(v, red4, &total);
         if (t < tiles) tile_sums[t] = carry + ex;
         carry += total;
     }
@@ -184,7 +163,7 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(int* __restrict__ a, in
     int v2 = b + 2 < m ? a[b + 2] : 0;
     int v3 = b + 3 < m ? a[b + 3] : 0;
     int total;
-    const int run = block_excl_scan256(v0 + v1 + v2 + v3, red4, &total) + tile_off[blockIdx.x];
+    const int run = block_excl_scan<4>(v0 + v1 + v2 + v3, red4, &total) + tile_off[blockIdx.x];
     if (b + 0 < m) a[b + 0] = run;
     if (b + 1 < m) a[b + 1] = run + v0;
     if (b + 2 < m) a[b + 2] = run + v0 + v1;
@@ -204,62 +183,19 @@ __global__ __launch_bounds__(256) void grid_scatter_kernel(const double* __restr
 }
 
 // --------------------------------------------------------------------------------------------------------- search
-// the cross-lane moves of knn_outer.hip's list: DPP wave_shr:1 (lane 0 keeps its own) and v_readlane
-__device__ __forceinline__ int grid_shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double grid_shr1_d(double v) {
-    return __hiloint2double(grid_shr1_i(__double2hiint(v)), grid_shr1_i(__double2loint(v)));
-}
-__device__ __forceinline__ double grid_readlane_d(double v, int lane_uniform) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
-}
-
-struct GridList {
-    double d;         // this lane's entry of the sorted list (squared distance, point index)
-    int i;
-    double tau_d;     // entry k-1 (wave-uniform)
-    int tau_i;
-};
-
 // every point of the sorted range [a, b) against the list
-__device__ __forceinline__ void grid_scan_range(GridList& L, int a, int b, double qx, double qy, double qz,
+__device__ __forceinline__ void grid_scan_range(WaveTopK<false, true>& L, int a, int b, double qx, double qy, double qz,
                                                 const double* __restrict__ sx, const double* __restrict__ sy,
-                                                const double* __restrict__ sz, const int* __restrict__ sidx, int k, int lane) {
-    const double INF = __builtin_huge_val();
+                                                const double* __restrict__ sz, const int* __restrict__ sidx, int lane) {
     for (int off = a; off < b; off += 64) {
         const int j = off + lane;
-        double d = INF;
+        double d = __builtin_huge_val();
         int pi = 0x7fffffff;
         if (j < b) {
-            const double dx = __dsub_rn(qx, sx[j]);
-            const double dy = __dsub_rn(qy, sy[j]);
-            const double dz = __dsub_rn(qz, sz[j]);
-            d = __dmul_rn(dx, dx);
-            d = __dadd_rn(d, __dmul_rn(dy, dy));
-            d = __dadd_rn(d, __dmul_rn(dz, dz));
+            d = dist2_rn(qx, qy, qz, sx[j], sy[j], sz[j]);
             pi = sidx[j];
         }
-        unsigned long long mask = __ballot(j < b && (d < L.tau_d || (d == L.tau_d && pi < L.tau_i)));
-        while (mask) {
-            const int src = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const double cd = grid_readlane_d(d, src);
-            const int ci = __builtin_amdgcn_readlane(pi, src);
-            if (!(cd < L.tau_d || (cd == L.tau_d && ci < L.tau_i))) continue;
-            // position = number of entries below the candidate's key; entries at and above it move up one lane
-            const int pos = __popcll(__ballot(L.d < cd || (L.d == cd && L.i < ci)));
-            const double ud = grid_shr1_d(L.d);
-            const int ui = grid_shr1_i(L.i);
-            if (lane == pos) {
-                L.d = cd;
-                L.i = ci;
-            } else if (lane > pos) {
-                L.d = ud;
-                L.i = ui;
-            }
-            L.tau_d = grid_readlane_d(L.d, k - 1);
-            L.tau_i = __builtin_amdgcn_readlane(L.i, k - 1);
-        }
+        L.offer(d, pi);
     }
 }
 
@@ -276,16 +212,15 @@ __global__ __launch_bounds__(256) void knn_self_grid_kernel(const double* __rest
     const int cx = grid_coord(qx, p.ox, p.h, p.gx);
     const int cy = grid_coord(qy, p.oy, p.h, p.gy);
     const int cz = grid_coord(qz, p.oz, p.h, p.gz);
-    const double INF = __builtin_huge_val();
-    GridList L{INF, 0x7fffffff, INF, 0x7fffffff};
+    WaveTopK<false, true> L(k);
     grid_shell_walk(
         p, start, cx, cy, cz, qx, qy, qz, p.slack,
-        [&](int a, int b) { grid_scan_range(L, a, b, qx, qy, qz, sx, sy, sz, sidx, k, lane); },
-        [&](double bnd) { return grid_bound_clears(bnd, L.tau_d); });                      // against the k-th squared distance
+        [&](int a, int b) { grid_scan_range(L, a, b, qx, qy, qz, sx, sy, sz, sidx, lane); },
+        [&](double bnd) { return grid_bound_clears(bnd, L.tau); });                      // against the k-th squared distance
     if (lane < k) {
         const int64_t o = (qi - row0) * k + lane;
-        idx_out[o] = L.i;
-        dist_out[o] = sqrt_cr(L.d);
+        idx_out[o] = L.i[0];
+        dist_out[o] = sqrt_cr(L.d[0]);
     }
 }
 
@@ -387,30 +322,6 @@ int launch_knn_self_grid(const double* pts, int64_t n, int64_t row0, int64_t row
 }
 
 // ----------------------------------------------------------------------------------------------------- statistics
-// numpy's pairwise leaf (n <= 128)
-__device__ __forceinline__ double np_leaf_sum(const double* __restrict__ a, int n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res = __dadd_rn(res, a[i]);
-        return res;
-    }
-    double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-        r0 = __dadd_rn(r0, a[i + 0]);
-        r1 = __dadd_rn(r1, a[i + 1]);
-        r2 = __dadd_rn(r2, a[i + 2]);
-        r3 = __dadd_rn(r3, a[i + 3]);
-        r4 = __dadd_rn(r4, a[i + 4]);
-        r5 = __dadd_rn(r5, a[i + 5]);
-        r6 = __dadd_rn(r6, a[i + 6]);
-        r7 = __dadd_rn(r7, a[i + 7]);
-    }
-    double res = __dadd_rn(__dadd_rn(__dadd_rn(r0, r1), __dadd_rn(r2, r3)), __dadd_rn(__dadd_rn(r4, r5), __dadd_rn(r6, r7)));
-    for (; i < n; ++i) res = __dadd_rn(res, a[i]);
-    return res;
-}
-
 // 64-thread workgroups.  Blocks [0, nchunks): the pairwise sum of one `bufsize`-element chunk of the flattened table (lane 0
 // lays the leaves out in LDS, the lanes sum them, lane 0 folds them back up the tree with an LDS stack); the blocks after
 // those: the row means, one row per thread.
@@ -430,65 +341,12 @@ __global__ __launch_bounds__(64) void outlier_stats_kernel(const double* __restr
     const int64_t c0 = (int64_t)blockIdx.x * bufsize;
     const int len = (int)((total - c0) < bufsize ? (total - c0) : bufsize);
     const double* a = dist + c0;
-    if (threadIdx.x == 0) {
-        int sp = 0, nl = 0;
-        st_o[sp] = 0;
-        st_l[sp] = len;
-        ++sp;
-        while (sp > 0) {
-            --sp;
-            const int o = st_o[sp], l = st_l[sp];
-            if (l <= 128) {
-                leaf_o[nl] = o;
-                leaf_l[nl] = l;
-                ++nl;
-            } else {
-                int n2 = l / 2;
-                n2 -= n2 % 8;
-                st_o[sp] = o + n2;                 // the right half pushed first: the left one is popped (and numbered) first
-                st_l[sp] = l - n2;
-                ++sp;
-                st_o[sp] = o;
-                st_l[sp] = n2;
-                ++sp;
-            }
-        }
-        nleaves = nl;
-    }
+    if (threadIdx.x == 0) nleaves = np_pairwise_plan<STATS_MAX_LEAVES>(len, leaf_o, leaf_l, st_o, st_l);
     __syncthreads();
     const int nl = nleaves;
     for (int j = threadIdx.x; j < nl; j += 64) leaf_s[j] = np_leaf_sum(a + leaf_o[j], leaf_l[j]);
     __syncthreads();
-    if (threadIdx.x != 0) return;
-    // post-order: a node is pushed unexpanded (e = 0); popped, an inner node goes back expanded (e = 1) under its two halves
-    int sp = 0, vsp = 0, leaf = 0;
-    st_l[sp] = len;
-    st_e[sp] = 0;
-    ++sp;
-    while (sp > 0) {
-        --sp;
-        const int l = st_l[sp];
-        if (st_e[sp]) {
-            const double rhs = vs[--vsp];
-            const double lhs = vs[--vsp];
-            vs[vsp++] = __dadd_rn(lhs, rhs);
-        } else if (l <= 128) {
-            vs[vsp++] = leaf_s[leaf++];
-        } else {
-            int n2 = l / 2;
-            n2 -= n2 % 8;
-            st_l[sp] = l;
-            st_e[sp] = 1;
-            ++sp;
-            st_l[sp] = l - n2;
-            st_e[sp] = 0;
-            ++sp;
-            st_l[sp] = n2;
-            st_e[sp] = 0;
-            ++sp;
-        }
-    }
-    chunk_sum[blockIdx.x] = vs[0];
+    if (threadIdx.x == 0) chunk_sum[blockIdx.x] = np_pairwise_fold<double, STATS_MAX_LEAVES>(len, leaf_s, st_l, st_e, vs);
 }
 
 __global__ __launch_bounds__(256) void outlier_keep_kernel(const double* __restrict__ row_mean, int64_t rows, double mean,

@@ -15,7 +15,11 @@
 //     current k-th distance, which yields the (distance, index) ascending order of a stable sort;
 //   * the FIRST 64-point slab does not go through 64 serial insertions (every one of them passes an empty list's
 //     threshold): it is sorted across the lanes by a bitonic network on (distance, index) keys and becomes the list.
+// The list is the arrival-order WaveTopK of wave_ops.h, written out: through the shared type this kernel, the one bench.py times,
+// ran 6 % slower (profiles/wave_ops_ab.txt, section 3), so the insertion stays here, on the header's cross-lane moves.  A change
+// to the tie rule belongs in both places; tests/test_gpu_parity.py (test_outer_knn_*) and tests/test_gpu_data.py hold both to it.
 #include "common.h"
+#include "wave_ops.h"
 
 namespace sapcu {
 
@@ -26,18 +30,6 @@ struct TopSlot {
     double d;
     int i;
 };
-
-// Cross-lane moves without the LDS crossbar: ds_bpermute (what __shfl compiles to) has ~100 cycles of
-// latency and an insertion chains ~15 of them; a wave-uniform source lane is a v_readlane, and "take the
-// value of lane-1" is one DPP move (wave_shr:1, lane 0 keeps its own).
-__device__ __forceinline__ int shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double shr1_d(double v) {
-    return __hiloint2double(shr1_i(__double2hiint(v)), shr1_i(__double2loint(v)));
-}
-__device__ __forceinline__ double readlane_d(double v, int lane_uniform) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
-}
 
 // TWO = the list needs the second slot per lane (k > 64); the model's k = 48 and the outlier filter's k = 30 run the
 // one-slot instance, whose insertion is a third shorter.
@@ -77,12 +69,7 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
             const int j = off + lane;
             double d = INF;
             if (j < cnt) {
-                const double dx = __dsub_rn(qx, tile[0][j]);
-                const double dy = __dsub_rn(qy, tile[1][j]);
-                const double dz = __dsub_rn(qz, tile[2][j]);
-                d = __dmul_rn(dx, dx);
-                d = __dadd_rn(d, __dmul_rn(dy, dy));
-                d = __dadd_rn(d, __dmul_rn(dz, dz));
+                d = dist2_rn(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]);
             }
             if (base == 0 && off == 0) {
                 // the list is empty: entries 0..63 = this slab in (distance, index) order (lanes past the cloud: INF, last)
@@ -103,27 +90,27 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
                 }
                 s0.d = d;
                 s0.i = si == 0x7fffffff ? -1 : si;
-                if (!TWO || k <= 64) tau = readlane_d(s0.d, (k - 1) & 63);      // k <= 64: the list is full (INF while cnt < k)
+                if (!TWO || k <= 64) tau = wave_readlane(s0.d, (k - 1) & 63);      // k <= 64: the list is full (INF while cnt < k)
                 continue;
             }
             unsigned long long mask = __ballot(d < tau);
             while (mask) {
                 const int src = __builtin_ctzll(mask);
                 mask &= mask - 1;
-                const double cd = readlane_d(d, src);
+                const double cd = wave_readlane(d, src);
                 if (!(cd < tau)) continue;
                 const int ci = (int)(base + off + src);
                 // position = number of entries <= candidate (all have smaller point index)
                 int pos = __popcll(__ballot(s0.d <= cd));
                 if (TWO) pos += __popcll(__ballot(s1.d <= cd));
                 // shift entries at positions >= pos up by one, drop the last
-                const double u0d = shr1_d(s0.d);
-                const int u0i = shr1_i(s0.i);
+                const double u0d = wave_shr1(s0.d);
+                const int u0i = wave_shr1(s0.i);
                 const int p0 = lane, p1 = lane + 64;
                 double l63d = 0.0;                                  // entry 63 moves into the second slot's lane 0
                 int l63i = 0;
                 if (TWO) {
-                    l63d = readlane_d(s0.d, 63);
+                    l63d = wave_readlane(s0.d, 63);
                     l63i = __builtin_amdgcn_readlane(s0.i, 63);
                 }
                 if (p0 == pos) {
@@ -134,8 +121,8 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
                     s0.i = u0i;
                 }
                 if (TWO) {
-                    double u1d = shr1_d(s1.d);
-                    int u1i = shr1_i(s1.i);
+                    double u1d = wave_shr1(s1.d);
+                    int u1i = wave_shr1(s1.i);
                     if (lane == 0) {
                         u1d = l63d;
                         u1i = l63i;
@@ -150,7 +137,7 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
                 }
                 // new k-th distance
                 const int kl = (k - 1) & 63;
-                tau = (!TWO || (k - 1) < 64) ? readlane_d(s0.d, kl) : readlane_d(s1.d, kl);
+                tau = (!TWO || (k - 1) < 64) ? wave_readlane(s0.d, kl) : wave_readlane(s1.d, kl);
             }
         }
     }

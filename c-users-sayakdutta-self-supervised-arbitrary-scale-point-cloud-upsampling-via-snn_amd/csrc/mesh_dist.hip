@@ -235,8 +235,7 @@ __global__ __launch_bounds__(256) void mesh_classify_kernel(const double* __rest
             r = 0.0;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) r = fmax(r, __shfl_xor(r, o));
+    r = wave_max(r);
     if ((threadIdx.x & 63) == 0 && r > 0.0) atomicMax(&ctl->rbits, (unsigned long long)__double_as_longlong(r));
 }
 

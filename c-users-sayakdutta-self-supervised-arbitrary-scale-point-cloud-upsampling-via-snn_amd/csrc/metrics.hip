@@ -94,12 +94,7 @@ __device__ __forceinline__ void cross_scan_range(CrossBest& B, int a, int b, dou
 #pragma unroll 4
         for (int t = 0; t < cnt; ++t) {
             const CrossPt p = slab[t];                                      // one address for the whole wave: a broadcast
-            const double dx = __dsub_rn(qx, p.x);
-            const double dy = __dsub_rn(qy, p.y);
-            const double dz = __dsub_rn(qz, p.z);
-            double d = __dmul_rn(dx, dx);
-            d = __dadd_rn(d, __dmul_rn(dy, dy));
-            d = __dadd_rn(d, __dmul_rn(dz, dz));
+            const double d = dist2_rn(qx, qy, qz, p.x, p.y, p.z);
             if (d < B.d || (d == B.d && p.idx < B.i)) {
                 B.d = d;
                 B.i = p.idx;

@@ -37,44 +37,7 @@ __device__ __forceinline__ float pd_dist2(float ax, float ay, float az, float bx
 }
 
 // ---------------------------------------------------------------------------------------------------------- resident
-// exclusive scan of one int per thread over the work group; scr: PD_WAVES ints, free again on return
-__device__ __forceinline__ int pd_block_excl_scan(int v, int* scr, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) scr[wave] = x;
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < PD_WAVES; ++w) {
-        const int t = scr[w];
-        if (w < wave) off += t;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return off + x - v;
-}
-
-// the minimum (or maximum) of one float per thread over the work group, in every thread; scr: PD_WAVES floats, free again on return
-template <bool MIN>
-__device__ __forceinline__ float pd_block_extreme(float v, float* scr) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float w = __shfl_xor(v, o);
-        v = MIN ? fminf(v, w) : fmaxf(v, w);
-    }
-    if ((threadIdx.x & 63) == 0) scr[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = scr[0];
-    for (int k = 1; k < PD_WAVES; ++k) r = MIN ? fminf(r, scr[k]) : fmaxf(r, scr[k]);
-    __syncthreads();
-    return r;
-}
-
+// (the block scan and the block extremes are wave_ops.h's, over PD_WAVES wavefronts; their scratch is L.scr)
 // One sorted slot is a float4 {x, y, z, word}: a candidate costs its reader ONE LDS read.  word = state in bits 0..2, the cell key
 // in bits 3..14, the row (= priority) from bit 15 up; only the slot's owner writes it, a 32-bit store.
 struct PdLds {
@@ -160,7 +123,7 @@ __device__ int pd_resident_select(const float* __restrict__ P, int C, int n2, co
             s += v[j];
         }
         int total;
-        int run = pd_block_excl_scan(s, L.scr, &total);
+        int run = block_excl_scan<PD_WAVES>(s, L.scr, &total);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int c = tid * 4 + j;
@@ -249,7 +212,7 @@ __device__ int pd_resident_select(const float* __restrict__ P, int C, int n2, co
     int mine = 0;
     for (int s = tid; s < C; s += PD_THREADS) mine += (pd_word(L.pt[s]) & PD_STATE_MASK) == PD_ACCEPTED;
     int total;
-    pd_block_excl_scan(mine, L.scr, &total);
+    block_excl_scan<PD_WAVES>(mine, L.scr, &total);
     return total;
 }
 
@@ -286,13 +249,13 @@ __global__ __launch_bounds__(PD_THREADS) void pd_resident_kernel(const float* __
         hz = fmaxf(hz, z);
     }
     float* fscr = reinterpret_cast<float*>(L.scr);
-    lx = pd_block_extreme<true>(lx, fscr);
-    ly = pd_block_extreme<true>(ly, fscr);
-    lz = pd_block_extreme<true>(lz, fscr);
-    hx = pd_block_extreme<false>(hx, fscr);
-    hy = pd_block_extreme<false>(hy, fscr);
-    hz = pd_block_extreme<false>(hz, fscr);
-    bad = pd_block_extreme<false>(bad, fscr);
+    lx = block_min<PD_WAVES>(lx, fscr);
+    ly = block_min<PD_WAVES>(ly, fscr);
+    lz = block_min<PD_WAVES>(lz, fscr);
+    hx = block_max<PD_WAVES>(hx, fscr);
+    hy = block_max<PD_WAVES>(hy, fscr);
+    hz = block_max<PD_WAVES>(hz, fscr);
+    bad = block_max<PD_WAVES>(bad, fscr);
     const PdBox bx{lx, ly, lz, hx, hy, hz};
 
     if (bad != 0.f) {                                                    // a box that is not finite keeps nothing (uniform branch)
@@ -345,7 +308,7 @@ __global__ __launch_bounds__(PD_THREADS) void pd_resident_kernel(const float* __
     int mine = 0;
     for (int i = first; i < min(first + per, C); ++i) mine += L.kept[i];
     int total;
-    int pos = pd_block_excl_scan(mine, L.scr, &total);
+    int pos = block_excl_scan<PD_WAVES>(mine, L.scr, &total);
     for (int i = first; i < min(first + per, C); ++i) {
         if (!L.kept[i]) continue;
         if (pos < n) idx_out[e * n + pos] = i;

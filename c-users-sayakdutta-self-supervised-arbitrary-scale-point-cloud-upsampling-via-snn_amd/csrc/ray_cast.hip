@@ -243,12 +243,9 @@ __global__ __launch_bounds__(64) void ray_setup_kernel(const double* __restrict_
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            lo[c] = fmin(lo[c], __shfl_xor(lo[c], o));
-            hi[c] = fmax(hi[c], __shfl_xor(hi[c], o));
-        }
+    for (int c = 0; c < 3; ++c) {
+        lo[c] = wave_min(lo[c]);
+        hi[c] = wave_max(hi[c]);
     }
     if (threadIdx.x != 0) return;
     if (bad != 0.0) {
@@ -303,9 +300,7 @@ __global__ __launch_bounds__(256) void ray_clip_kernel(const double* __restrict_
         cy = o[1] + t0 * d[1];
         cz = o[2] + t0 * d[2];
     }
-    int sum = valid ? np : 0;                                                     // the wavefront's pieces: one integer atomic
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+    const int sum = wave_sum(valid ? np : 0);                                     // the wavefront's pieces: one integer atomic
     if (valid) {
         corg[i * 3 + 0] = cx;
         corg[i * 3 + 1] = cy;
@@ -315,18 +310,6 @@ __global__ __launch_bounds__(256) void ray_clip_kernel(const double* __restrict_
         np_out[i] = np;
     }
     if ((threadIdx.x & 63) == 0 && sum > 0) atomicAdd(&ctl->pieces, (unsigned long long)sum);
-}
-
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return __builtin_amdgcn_readfirstlane(v);
 }
 
 __global__ __launch_bounds__(256) void ray_grid_kernel(const GridParams* __restrict__ prm, const int* __restrict__ start,
@@ -355,7 +338,7 @@ __global__ __launch_bounds__(256) void ray_grid_kernel(const GridParams* __restr
     const double dmax = fmax(fmax(fabs(r.dx), fabs(r.dy)), fabs(r.dz));
     const double tslack = np > 0 ? p.slack / dmax : 0.0;
     const double span = t1 - t0;
-    const int kmax = wave_max_int(np);
+    const int kmax = wave_max_uniform(np);
     double ta = t0;
     for (int k = 0; k < kmax; ++k) {
         const double tb = k + 1 >= np ? t1 : t0 + span * ((double)(k + 1) / (double)np);
@@ -372,8 +355,8 @@ __global__ __launch_bounds__(256) void ray_grid_kernel(const GridParams* __restr
             z0 = grid_coord(fmin(az, bz) - margin, p.oz, p.h, p.gz);
             z1 = grid_coord(fmax(az, bz) + margin, p.oz, p.h, p.gz);
         }
-        const int X0 = wave_min_int(x0), Y0 = wave_min_int(y0), Z0 = wave_min_int(z0);
-        const int X1 = wave_max_int(x1), Y1 = wave_max_int(y1), Z1 = wave_max_int(z1);
+        const int X0 = wave_min_uniform(x0), Y0 = wave_min_uniform(y0), Z0 = wave_min_uniform(z0);
+        const int X1 = wave_max_uniform(x1), Y1 = wave_max_uniform(y1), Z1 = wave_max_uniform(z1);
         for (int z = Z0; z <= Z1; ++z) {
             for (int y = Y0; y <= Y1; ++y) {
                 const int row = (z * p.gy + y) * p.gx;

@@ -10,7 +10,7 @@
 //   * area sum, one 128-thread workgroup per mesh: numpy's pairwise tree over every 8192-element chunk, the chunk sums added in
 //     sequence.  A full chunk's tree is perfect (64 leaves of 128 values): one leaf per lane with eight accumulators, then six
 //     levels of neighbour pairs through LDS.  The last, shorter chunk: lane 0 lays its leaves (64..128 values each) out in LDS, one
-//     leaf per lane, lane 0 folds them back up the tree with an LDS stack (the scheme of knn_grid.hip's outlier statistics, in f32).
+//     leaf per lane, lane 0 folds them back up the tree with an LDS stack (leaf, plan and fold: wave_ops.h, in f32).
 //   * cdf, one 256-thread workgroup per mesh: 1024-face tiles of p = (double)(area / denom) go coalesced into LDS, lane 0 runs the
 //     dependent f64 add chain through the tile in place, all threads store the running sums; a second pass divides by the last one
 //     (every thread re-reads what it wrote itself).  Bound by the F-step add chain: 15 ns per face, and keeping the next LDS reads
@@ -19,6 +19,7 @@
 // dependent f64 loads, L2 hits), three face indices, nine coordinates and the normal gathered, 11 f32 operations and one root.
 // No scratch, no atomics.
 #include "common.h"
+#include "wave_ops.h"
 #include "../../include/sapcu_surface.h"
 
 namespace sapcu {
@@ -96,30 +97,6 @@ __global__ __launch_bounds__(256) void ss_face_kernel(SsMeshes ms, float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------- area sum
-// numpy's pairwise leaf (n <= 128) in f32
-__device__ __forceinline__ float ss_leaf_sum(const float* __restrict__ a, int n) {
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; ++i) res = __fadd_rn(res, a[i]);
-        return res;
-    }
-    float r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-        r0 = __fadd_rn(r0, a[i + 0]);
-        r1 = __fadd_rn(r1, a[i + 1]);
-        r2 = __fadd_rn(r2, a[i + 2]);
-        r3 = __fadd_rn(r3, a[i + 3]);
-        r4 = __fadd_rn(r4, a[i + 4]);
-        r5 = __fadd_rn(r5, a[i + 5]);
-        r6 = __fadd_rn(r6, a[i + 6]);
-        r7 = __fadd_rn(r7, a[i + 7]);
-    }
-    float res = __fadd_rn(__fadd_rn(__fadd_rn(r0, r1), __fadd_rn(r2, r3)), __fadd_rn(__fadd_rn(r4, r5), __fadd_rn(r6, r7)));
-    for (; i < n; ++i) res = __fadd_rn(res, a[i]);
-    return res;
-}
-
 __global__ __launch_bounds__(128) void ss_area_sum_kernel(const int64_t* __restrict__ face_off, int64_t total_faces,
                                                           const float* __restrict__ area, float* __restrict__ sums) {
     __shared__ int leaf_o[SS_MAX_LEAVES], leaf_l[SS_MAX_LEAVES];
@@ -136,7 +113,7 @@ __global__ __launch_bounds__(128) void ss_area_sum_kernel(const int64_t* __restr
         const int len = min(count - c0, SS_CHUNK);
         const float* a = area + fr.first + c0;
         if (len == SS_CHUNK) {                                   // (block-uniform) a full chunk's tree is perfect: 64 leaves of 128 values,
-            if (tid < 64) leaf_s[tid] = ss_leaf_sum(a + tid * 128, 128);      // neighbours added pair by pair, level by level
+            if (tid < 64) leaf_s[tid] = np_leaf_sum(a + tid * 128, 128);      // neighbours added pair by pair, level by level
             __syncthreads();
             for (int s = 1; s < 64; s <<= 1) {
                 if (tid < 64 && (tid & (2 * s - 1)) == 0) leaf_s[tid] = __fadd_rn(leaf_s[tid], leaf_s[tid + s]);   // tid + s is idle at this level
@@ -146,67 +123,12 @@ __global__ __launch_bounds__(128) void ss_area_sum_kernel(const int64_t* __restr
             __syncthreads();                                     // leaf_s is rewritten by the next chunk
             continue;
         }
-        if (tid == 0) {
-            int sp = 0, nl = 0;
-            st_o[sp] = 0;
-            st_l[sp] = len;
-            ++sp;
-            while (sp > 0 && nl < SS_MAX_LEAVES) {
-                --sp;
-                const int o = st_o[sp], l = st_l[sp];
-                if (l <= 128) {
-                    leaf_o[nl] = o;
-                    leaf_l[nl] = l;
-                    ++nl;
-                } else {
-                    int n2 = l / 2;
-                    n2 -= n2 % 8;
-                    st_o[sp] = o + n2;             // the right half pushed first: the left one is popped (and numbered) first
-                    st_l[sp] = l - n2;
-                    ++sp;
-                    st_o[sp] = o;
-                    st_l[sp] = n2;
-                    ++sp;
-                }
-            }
-            nleaves = nl;
-        }
+        if (tid == 0) nleaves = np_pairwise_plan<SS_MAX_LEAVES>(len, leaf_o, leaf_l, st_o, st_l);
         __syncthreads();
         const int nl = nleaves;
-        for (int j = tid; j < nl; j += 128) leaf_s[j] = ss_leaf_sum(a + leaf_o[j], leaf_l[j]);
+        for (int j = tid; j < nl; j += 128) leaf_s[j] = np_leaf_sum(a + leaf_o[j], leaf_l[j]);
         __syncthreads();
-        if (tid == 0) {
-            // post-order: a node is pushed unexpanded (e = 0); popped, an inner node goes back expanded (e = 1) under its two halves
-            int sp = 0, vsp = 0, leaf = 0;
-            st_l[sp] = len;
-            st_e[sp] = 0;
-            ++sp;
-            while (sp > 0) {
-                --sp;
-                const int l = st_l[sp];
-                if (st_e[sp]) {
-                    const float rhs = vs[--vsp];
-                    const float lhs = vs[--vsp];
-                    vs[vsp++] = __fadd_rn(lhs, rhs);
-                } else if (l <= 128) {
-                    vs[vsp++] = leaf_s[leaf < SS_MAX_LEAVES ? leaf : SS_MAX_LEAVES - 1];
-                    ++leaf;
-                } else {
-                    int n2 = l / 2;
-                    n2 -= n2 % 8;
-                    st_l[sp] = l;
-                    st_e[sp] = 1;
-                    ++sp;
-                    st_l[sp] = l - n2;
-                    st_e[sp] = 0;
-                    ++sp;
-                    st_l[sp] = n2;
-                    st_e[sp] = 0;
-                    ++sp;
-                }
-            }
-            total = __fadd_rn(total, vs[0]);
-        }
+        if (tid == 0) total = __fadd_rn(total, np_pairwise_fold<float, SS_MAX_LEAVES>(len, leaf_s, st_l, st_e, vs));
         // (lane 0 rewrites the leaf table only after the next barrier-free stretch of its own: the other lanes read it between the
         //  two barriers above, and wait at the first one of the next chunk)
     }

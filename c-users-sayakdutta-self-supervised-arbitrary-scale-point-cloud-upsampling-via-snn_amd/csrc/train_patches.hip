@@ -13,10 +13,11 @@
 //     four partial minima are combined through LDS (a minimum does not depend on the order).  f64 VALU.
 //   * neighbours, one workgroup per (entry, 8 centres): the entry's normalised cloud in LDS (f32 SoA, 12 n bytes of dynamic LDS), one
 //     centre per wave at a time;
-//     the k-list is the scheme of knn_outer.hip — a sorted list spread over the lanes, the first 64-point slab sorted by a bitonic
-//     network on (distance, index), later candidates in ascending index against the k-th distance with strict '<'.  f64 VALU.
+//     the k-list is WaveTopK in arrival order (wave_ops.h) — a sorted list spread over the lanes, the first 64-point slab sorted by
+//     a bitonic network on (distance, index), later candidates in ascending index against the k-th distance with strict '<'.  f64 VALU.
 // No scratch, no atomics.
 #include "common.h"
+#include "wave_ops.h"
 #include "../../include/sapcu_data.h"
 
 namespace sapcu {
@@ -85,13 +86,6 @@ __device__ __forceinline__ TpPoint tp_normal(const float* __restrict__ nrm, cons
     return TpPoint{__fdiv_rn(p.x, den), __fdiv_rn(p.y, den), __fdiv_rn(p.z, den)};
 }
 
-__device__ __forceinline__ double tp_dist2(double qx, double qy, double qz, float px, float py, float pz) {
-    const double dx = __dsub_rn(qx, (double)px);
-    const double dy = __dsub_rn(qy, (double)py);
-    const double dz = __dsub_rn(qz, (double)pz);
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
 // ------------------------------------------------------------------------------------------------------------ prepare
 __global__ __launch_bounds__(256) void tp_prepare_kernel(const float* __restrict__ clouds, int64_t n_samples, int n,
                                                          const float* __restrict__ dense, int g, const float* __restrict__ normals,
@@ -134,8 +128,7 @@ __global__ __launch_bounds__(256) void tp_prepare_kernel(const float* __restrict
         tile[2][p] = z;
         m = fmaxf(m, __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if ((tid & 63) == 0) wmax[tid >> 6] = m;
     __syncthreads();
     if (tid == 0) st[3] = tp_sqrtf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])));
@@ -213,10 +206,10 @@ __global__ __launch_bounds__(256) void tp_len_kernel(const float* __restrict__ d
         int j = j0;
 #pragma unroll 4
         for (; j + 1 < j1; j += 2) {
-            best = fmin(best, tp_dist2(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]));
-            other = fmin(other, tp_dist2(qx, qy, qz, tile[0][j + 1], tile[1][j + 1], tile[2][j + 1]));
+            best = fmin(best, dist2_rn(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]));
+            other = fmin(other, dist2_rn(qx, qy, qz, tile[0][j + 1], tile[1][j + 1], tile[2][j + 1]));
         }
-        if (j < j1) best = fmin(best, tp_dist2(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]));
+        if (j < j1) best = fmin(best, dist2_rn(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]));
         best = fmin(best, other);
     }
     part[wave][lane] = best;
@@ -228,21 +221,6 @@ __global__ __launch_bounds__(256) void tp_len_kernel(const float* __restrict__ d
 }
 
 // ---------------------------------------------------------------------------------------------------------- neighbours
-struct TpSlot {
-    double d;
-    int i;
-};
-
-// (the cross-lane moves of knn_outer.hip: wave_shr:1 as one DPP move, a wave-uniform source lane as v_readlane)
-__device__ __forceinline__ int tp_shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double tp_shr1_d(double v) {
-    return __hiloint2double(tp_shr1_i(__double2hiint(v)), tp_shr1_i(__double2loint(v)));
-}
-__device__ __forceinline__ double tp_readlane_d(double v, int lane_uniform) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane_uniform),
-                            __builtin_amdgcn_readlane(__double2loint(v), lane_uniform));
-}
-
 // TWO = the list needs the second slot per lane (k > 64); fd's k = 32 and fn's k = 12 run the one-slot instance.
 template <bool TWO>
 __global__ __launch_bounds__(256) void tp_knn_kernel(const float* __restrict__ cloud_out, int n, const float* __restrict__ normals,
@@ -271,84 +249,19 @@ __global__ __launch_bounds__(256) void tp_knn_kernel(const float* __restrict__ c
         const int centre = centres ? centres[bi * pc + ci] : ci;
         if (centre < 0 || centre >= n) continue;                 // a bad centre: its rows are not written (wave-uniform)
         const double qx = tile[0][centre], qy = tile[1][centre], qz = tile[2][centre];
-        TpSlot s0{INF, -1}, s1{INF, -1};
-        double tau = INF;                                        // distance of list entry k-1 (wave-uniform)
+        WaveTopK<TWO> top(k);
         for (int off = 0; off < n; off += 64) {
             const int j = off + lane;
-            double d = INF;
-            if (j < n) d = tp_dist2(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]);
-            if (off == 0) {
-                // the list is empty: entries 0..63 = this slab in (distance, index) order (lanes past the cloud: INF, last)
-                int si = j < n ? j : 0x7fffffff;
-#pragma unroll
-                for (int kb = 2; kb <= 64; kb <<= 1) {
-#pragma unroll
-                    for (int jb = kb >> 1; jb > 0; jb >>= 1) {
-                        const double od = __shfl_xor(d, jb);
-                        const int oi = __shfl_xor(si, jb);
-                        const bool own_less = d < od || (d == od && si < oi);
-                        const bool want_less = ((lane & jb) == 0) == ((lane & kb) == 0);     // lower lane of an ascending pair
-                        if (own_less != want_less) {
-                            d = od;
-                            si = oi;
-                        }
-                    }
-                }
-                s0.d = d;
-                s0.i = si == 0x7fffffff ? -1 : si;
-                if (!TWO || k <= 64) tau = tp_readlane_d(s0.d, (k - 1) & 63);
-                continue;
-            }
-            unsigned long long mask = __ballot(d < tau);
-            while (mask) {
-                const int src = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const double cd = tp_readlane_d(d, src);
-                if (!(cd < tau)) continue;
-                const int cidx = off + src;
-                int pos = __popcll(__ballot(s0.d <= cd));        // entries <= candidate all have a smaller point index
-                if (TWO) pos += __popcll(__ballot(s1.d <= cd));
-                const double u0d = tp_shr1_d(s0.d);
-                const int u0i = tp_shr1_i(s0.i);
-                const int p0 = lane, p1 = lane + 64;
-                double l63d = 0.0;                               // entry 63 moves into the second slot's lane 0
-                int l63i = 0;
-                if (TWO) {
-                    l63d = tp_readlane_d(s0.d, 63);
-                    l63i = __builtin_amdgcn_readlane(s0.i, 63);
-                }
-                if (p0 == pos) {
-                    s0.d = cd;
-                    s0.i = cidx;
-                } else if (p0 > pos) {
-                    s0.d = u0d;
-                    s0.i = u0i;
-                }
-                if (TWO) {
-                    double u1d = tp_shr1_d(s1.d);
-                    int u1i = tp_shr1_i(s1.i);
-                    if (lane == 0) {
-                        u1d = l63d;
-                        u1i = l63i;
-                    }
-                    if (p1 == pos) {
-                        s1.d = cd;
-                        s1.i = cidx;
-                    } else if (p1 > pos) {
-                        s1.d = u1d;
-                        s1.i = u1i;
-                    }
-                }
-                const int kl = (k - 1) & 63;
-                tau = (!TWO || (k - 1) < 64) ? tp_readlane_d(s0.d, kl) : tp_readlane_d(s1.d, kl);
-            }
+            const double d = j < n ? dist2_rn(qx, qy, qz, tile[0][j], tile[1][j], tile[2][j]) : INF;
+            if (off == 0) top.first_slab(d, j < n ? j : 0x7fffffff);      // lanes past the cloud: INF, last
+            else top.offer(d, off);
         }
         const int64_t row = (bi * pc + ci) * k;
 #pragma unroll
-        for (int slot = 0; slot < (TWO ? 2 : 1); ++slot) {
+        for (int slot = 0; slot < top.SLOTS; ++slot) {
             const int p = lane + 64 * slot;
             if (p >= k) continue;
-            const int i = slot == 0 ? s0.i : s1.i;
+            const int i = top.i[slot];
             const bool ok = i >= 0 && i < n;                     // (a non-finite cloud can leave entries empty: NaN rows, index -1)
             if (idx_out) idx_out[row + p] = ok ? i : -1;
             float* o = patches_out + (row + p) * 3;

@@ -52,6 +52,11 @@ def _make_case(name):
         "b1": (3, 80, 90, True, 1, 0, 16, True),
         "b17": (3, 80, 90, True, 17, 10, 16, True),
         "n1": (2, 1, 3, True, 2, 0, 1, True),
+        # the edges of the neighbour kernel's slot switch: the first slab alone, the largest one-slot list with insertions, both slots full
+        "k64-n64": (2, 64, 0, False, 2, 0, 64, False),
+        "k64-n130": (2, 130, 0, False, 2, 0, 64, True),
+        "k128-n128": (2, 128, 0, False, 2, 0, 128, False),
+        "k128-n193": (2, 193, 0, False, 2, 0, 128, True),
     }
     if name in shapes:
         S, n, g, nrm, b, pc, k, aug = shapes[name]
@@ -63,12 +68,13 @@ def _make_case(name):
              "jitter": (rng.normal(size=(b, n, 3)) * 0.002).astype(f32) if aug else None,
              "centres": rng.integers(0, n, size=(b, pc)).astype(np.int32) if pc else None, "k": k}
         return c
-    if name == "lattice":                                      # a shuffled 7^3 integer lattice: every distance is tied many times
+    if name in ("lattice", "lattice-k64"):                     # a shuffled 7^3 integer lattice: every distance is tied many times
+                                                               # (-k64: ties at the one-slot list's last entry)
         grid = np.stack(np.meshgrid(*[np.arange(7)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(f32)
         clouds = np.stack([grid[rng.permutation(343)] for _ in range(2)])
         dense = np.stack([(grid[rng.permutation(343)][:200] + 0.5).astype(f32) for _ in range(2)])
         return {"clouds": clouds, "dense": dense, "normals": None, "sidx": np.array([1, 0], np.int64), "rot": None, "scale": None,
-                "jitter": None, "centres": None, "k": 100}
+                "jitter": None, "centres": None, "k": 64 if name == "lattice-k64" else 100}
     if name == "duplicates":                                   # every point four times, shuffled: the lower index must come first
         base = rng.normal(size=(2, 50, 3)).astype(f32)
         clouds = np.stack([np.tile(base[s], (4, 1))[rng.permutation(200)] for s in range(2)])
@@ -90,7 +96,8 @@ def _make_case(name):
     raise KeyError(name)
 
 
-CASES = ["fd", "fn", "n100-k100", "k1", "g1", "k65-n129", "n4096", "lattice", "duplicates", "identical", "repeats", "b1", "b17", "n1"]
+CASES = ["fd", "fn", "n100-k100", "k1", "g1", "k65-n129", "n4096", "lattice", "duplicates", "identical", "repeats", "b1", "b17", "n1",
+         "k64-n64", "k64-n130", "k128-n128", "k128-n193", "lattice-k64"]
 _CACHE = {}
 
 
@@ -135,7 +142,7 @@ def test_every_output_equals_the_numpy_restatement(name):
     if name == "identical":
         assert (got["cloud"] == 0).all() and (got["len"] > 0).all() and (got["normals"][0, 5] == 0).all()
         assert (got["idx"] == np.arange(70)).all()             # all distances 0: ascending index
-    if name in ("lattice", "duplicates"):                      # the case is what it claims: ties inside the first k + 1 distances
+    if name in ("lattice", "lattice-k64", "duplicates"):       # the case is what it claims: ties inside the first k + 1 distances
         cloud = ref["cloud"][0]
         _, d = R.neighbours(cloud, np.arange(len(cloud)), c["k"] + 1, want_dist=True)
         assert (np.diff(d, axis=1) == 0).any(axis=1).all()
