@@ -17,7 +17,9 @@
 //     threshold): it is sorted across the lanes by a bitonic network on (distance, index) keys and becomes the list.
 // The list is the arrival-order WaveTopK of wave_ops.h, written out: through the shared type this kernel, the one bench.py times,
 // ran 6 % slower (profiles/wave_ops_ab.txt, section 3), so the insertion stays here, on the header's cross-lane moves.  A change
-// to the tie rule belongs in both places; tests/test_gpu_parity.py (test_outer_knn_*) and tests/test_gpu_data.py hold both to it.
+// to the tie rule belongs in both places.  tests/test_gpu_klist.py holds this copy to it at every k from 1 to 128 on clouds of exact
+// ties (and to the rule for non-finite distances: wave_ops.h), tests/test_gpu_wave_ops.py (tests/micro/wave_ops_probe.hip) the
+// header's; tests/test_gpu_parity.py (test_outer_knn_*) and tests/test_gpu_data.py reach both through the entry points.
 #include "common.h"
 #include "wave_ops.h"
 
@@ -73,7 +75,12 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
             }
             if (base == 0 && off == 0) {
                 // the list is empty: entries 0..63 = this slab in (distance, index) order (lanes past the cloud: INF, last)
+                // (a NaN or +inf distance: no candidate either — the rule of wave_ops.h; the network needs a total order)
                 int si = j < cnt ? j : 0x7fffffff;
+                if (!(d < INF)) {
+                    d = INF;
+                    si = 0x7fffffff;
+                }
 #pragma unroll
                 for (int kb = 2; kb <= 64; kb <<= 1) {
 #pragma unroll
@@ -147,14 +154,19 @@ __global__ __launch_bounds__(256) void knn_outer_kernel(const double* __restrict
         const int p = lane + 64 * slot;
         if (p >= k) continue;
         const TopSlot s = slot == 0 ? s0 : s1;
-        idx_out[qi * k + p] = s.i;
-        if (dist_out) dist_out[qi * k + p] = sqrt_cr(s.d);
+        const bool ok = s.i >= 0;                                // fewer than k finite distances leave entries empty: index -1,
+        idx_out[qi * k + p] = ok ? s.i : -1;                     // distance +inf, a NaN row, and no load through the index
+        if (dist_out) dist_out[qi * k + p] = ok ? sqrt_cr(s.d) : INF;
         if (patch_out) {
-            const double* pp = cloud + (int64_t)s.i * 3;
             float* o = patch_out + (qi * k + p) * 3;
-            o[0] = (float)__dsub_rn(pp[0], qx);
-            o[1] = (float)__dsub_rn(pp[1], qy);
-            o[2] = (float)__dsub_rn(pp[2], qz);
+            if (ok) {
+                const double* pp = cloud + (int64_t)s.i * 3;
+                o[0] = (float)__dsub_rn(pp[0], qx);
+                o[1] = (float)__dsub_rn(pp[1], qy);
+                o[2] = (float)__dsub_rn(pp[2], qz);
+            } else {
+                o[0] = o[1] = o[2] = __builtin_nanf("");
+            }
         }
     }
 }

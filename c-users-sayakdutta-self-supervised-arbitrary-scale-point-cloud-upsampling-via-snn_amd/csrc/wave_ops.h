@@ -120,7 +120,14 @@ __device__ __forceinline__ double dist2_rn(double qx, double qy, double qz, doub
 //   * keyed: the lexicographic (distance, index) compare, the k-th entry's index carried along; any arrival order.  offer() takes
 //     each lane's own index.
 // (knn_outer.hip keeps the arrival-order insertion written out, for its speed there: a change of the rule belongs in both.)
-// A lane without a candidate offers distance +inf (keyed: index INT_MAX); NaN distances never enter after the first slab.
+// A lane without a candidate offers distance +inf (keyed: index INT_MAX).
+// NON-FINITE CANDIDATES (arrival order; the rule of include/sapcu.h and DESIGN section 2): a candidate whose squared distance is
+// NaN or +inf is not a candidate.  The list holds the finite ones in (distance, index) order, then empty entries (+inf, NONE); a
+// kernel writes an empty entry as index -1, distance +inf and a NaN row, and loads nothing through it.  offer() keeps the rule for
+// nothing (NaN < tau and +inf < tau are false); first_slab() turns such a lane into a lane without a candidate before its
+// network, whose compare is no order once a NaN is in it.  The keyed list orders whatever is not NaN: there a +inf distance with
+// a real index stands behind the finite entries and in front of the empty ones; its user (knn_grid.hip) never offers one, the
+// grid is not built over non-finite coordinates.
 template <bool TWO, bool KEYED = false>
 struct WaveTopK {
     static_assert(!(TWO && KEYED), "the keyed list has no user beyond k = 64");
@@ -161,6 +168,10 @@ struct WaveTopK {
     // a bitonic network on (distance, index) keys sorts them across the lanes.  si: this lane's index, INT_MAX without a candidate.
     __device__ __forceinline__ void first_slab(double cd, int si) {
         const int lane = threadIdx.x & 63;
+        if (!(cd < __builtin_huge_val())) {       // NaN or +inf: no candidate (once per query; the network needs a total order)
+            cd = __builtin_huge_val();
+            si = 0x7fffffff;
+        }
 #pragma unroll
         for (int kb = 2; kb <= 64; kb <<= 1) {
 #pragma unroll

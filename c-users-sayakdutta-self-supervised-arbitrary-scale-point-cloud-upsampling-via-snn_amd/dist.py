@@ -175,8 +175,9 @@ def upsample_cloud_sharded(generator, data, group=None):
     """``generator.upsample(data)`` over the ranks of ``group``: every rank returns the same filtered ndarray [M',3] f64, bit for
     bit the single-process result with ``knn_cache_mode='fresh'`` (the sharded refine needs it; see upsample_sharded)."""
     from . import generation
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
     data = np.squeeze(data, 0) if np.ndim(data) == 3 else np.asarray(data)
+    generation.require_finite("the cloud", data)               # as generator.upsample: ValueError on every rank, before any launch
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
     if getattr(generator, "seed_source", None) == "device":     # every rank floods its own copy: deterministic, nothing to send
         seeds_dev = generator._dense_seeds(data)
     else:

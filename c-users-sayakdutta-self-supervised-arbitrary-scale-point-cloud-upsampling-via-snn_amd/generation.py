@@ -104,8 +104,18 @@ def dense_seeds_device(data, spacing, device, max_voxels=None, capacity=None, st
         return out[: count.value].clone()
 
 
+def require_finite(name, arr):
+    """sklearn's KDTree(data) and .query(q) raise ValueError on NaN or infinity (generation.py:110,127).  The entries that are
+    handed a host array (Generator3D6.generateiopoint / upsample_seeds, dist.upsample_cloud_sharded) do the same on that array,
+    before any launch; knn_gather and refine work on device tensors and follow the rule of include/sapcu.h instead."""
+    if not np.isfinite(arr).all():
+        raise ValueError("%s contains NaN or infinity" % name)
+
+
 def knn_gather(cloud_dev, queries_dev, k, want_dist=False, want_patch=True):
-    """Outer kNN on the device: (idx int64 [b,k], dist f64 [b,k] | None, patch f32 [b,k,3] | None)."""
+    """Outer kNN on the device: (idx int64 [b,k], dist f64 [b,k] | None, patch f32 [b,k,3] | None).  No host check and no
+    synchronisation: a cloud point at a NaN or +inf distance is no candidate, and a query with fewer than k finite distances
+    gets empty entries behind them (idx -1, dist +inf, a NaN patch row), see include/sapcu.h."""
     lib = _lib.load()
     b, n = queries_dev.shape[0], cloud_dev.shape[0]
     if k > n:      # sklearn's KDTree.query raises the same way (generation.py:127)
@@ -278,6 +288,7 @@ class Generator3D6(object):
 
     def generateiopoint(self, data):
         data = np.squeeze(data, 0) if np.ndim(data) == 3 else np.asarray(data)
+        require_finite("the cloud", data)
         seeds = self._dense_seeds(data)
         return self.upsample_seeds(data, seeds)
 
@@ -386,11 +397,16 @@ class Generator3D6(object):
         return outlier_filter_device(pts_dev, self.outlier_threshold, rows, gather_sums)
 
     def upsample_seeds(self, data, seeds, return_unfiltered=False):
-        cloud_dev = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float64), device=self.device)
-        if torch.is_tensor(seeds):          # seed_source = "device": already in HBM
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        require_finite("the cloud", data)
+        if not torch.is_tensor(seeds):
+            seeds = np.ascontiguousarray(seeds, dtype=np.float64)
+            require_finite("the seeds", seeds)
+        cloud_dev = torch.as_tensor(data, device=self.device)
+        if torch.is_tensor(seeds):          # seed_source = "device": already in HBM (flooded from the checked cloud)
             seeds_dev = seeds.to(device=self.device, dtype=torch.float64).contiguous()
         else:
-            seeds_dev = torch.as_tensor(np.ascontiguousarray(seeds, dtype=np.float64), device=self.device)
+            seeds_dev = torch.as_tensor(seeds, device=self.device)
         if seeds_dev.shape[0] == 0:        # nothing in the distance band (the reference fails inside np.loadtxt here)
             empty = np.zeros((0, 3), dtype=np.float64)
             return (empty, empty) if return_unfiltered else empty

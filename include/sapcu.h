@@ -69,7 +69,12 @@ const char* sapcu_last_error(void);
  * distances are sum_c (q_c-p_c)^2 accumulated x,y,z in f64 without FMA contraction.
  * dist_out [b,k] f64 (euclidean, i.e. sqrt) and patch_out [b,k,3] f32 are optional (NULL to
  * skip); patch_out = f32(cloud[idx] - q), the subtraction done in f64 (generation.py:128-129,137).
- * Requires 1 <= k <= 128 and k <= n. */
+ * Requires 1 <= k <= 128 and k <= n.
+ * Non-finite coordinates (the reference's KDTree raises on them; this call, on device memory, does not look): a cloud point
+ * whose squared distance to the query is NaN or +inf is not a candidate.  A row holds the finite ones in ascending
+ * (distance, index), then, if fewer than k are finite, empty entries: idx -1, dist +inf, a NaN patch row; nothing is loaded
+ * through an empty entry's index.  The same rule holds wherever the k-list of csrc/wave_ops.h is written out
+ * (the nearest-neighbour and grid kNN calls on their brute-force route, the training-patch builder of sapcu_data.h). */
 int sapcu_knn_gather_f64(const double* cloud, int64_t n, const double* queries, int64_t b, int k,
                          int64_t* idx_out, double* dist_out, float* patch_out, void* stream);
 

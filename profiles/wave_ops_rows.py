@@ -3,7 +3,8 @@
 workloads of knn_microbench.py, grid_walk_extra.py, train_patches.py, surface_sample.py, poisson.py, uniformity.py, metrics_nn.py,
 mesh_dist.py and ray_cast.py (their builders are imported), without those scripts' host comparisons and sweeps.  Every row is
 `runs` device-event times in ms after a warm-up, one line `ROW <name> | t t t ...`; a row of short calls times windows of
-back-to-back calls and prints ms per call.  Needs a GPU.  Usage: SAPCU_LIB_PATH=profiles/ab/libA.so wave_ops_rows.py [runs]"""
+back-to-back calls and prints ms per call.  Needs a GPU.  Usage: SAPCU_LIB_PATH=profiles/ab/libA.so wave_ops_rows.py [runs [knn_outer]]
+(the word knn_outer: the three rows of the outer kNN alone, profiles/klist_tests_ab.txt)."""
 import os
 import sys
 
@@ -50,6 +51,8 @@ def main():
     for b, k, calls in ((4096, 48, 20), (65536, 48, 5), (4096, 100, 20)):
         q = cloud[:b].contiguous() if b <= 5000 else many
         row("knn_outer N=5000 B=%d k=%d" % (b, k), lambda: gen.knn_gather(cloud, q, k), runs, calls)
+    if len(sys.argv) > 2 and sys.argv[2] == "knn_outer":
+        return
 
     # grid_walk_extra.py: seed generation, the self-kNN on the grid; the outlier statistics of its k = 30 table
     sphere = T.sphere_cloud(5000, 0)
