@@ -544,11 +544,14 @@ struct GemmArgs {
 int launch_gemm(const GemmArgs& g, hipStream_t st);        // f32 MFMA (exact f32 products)
 int launch_gemm_sf16(const GemmArgs& g, hipStream_t st);   // 3 x f16 MFMA, f32-quality (needs w16_hi/lo); f32 A
 int launch_gemm_sf16_ring(const GemmArgs& g, hipStream_t st);   // same arithmetic, A in split rows, 4-slot LDS-DMA ring
+bool gemm_sf16_ring_accepts(const GemmArgs& g, const char** why);    // ... what it takes (every empty call); *why: a refusal's text
 int launch_gemm_sf16_bt(const GemmArgs& g, hipStream_t st);     // same arithmetic and results, 256 x 256/128 tiles (gemm_sf16_bt.hip)
 bool gemm_sf16_bt_ok(const GemmArgs& g);                        // ... for the shapes / epilogues it takes
 bool gemm_shortk_ok(const GemmArgs& g);                         // f32 A, K in {64, 128, 192}, neuron epilogue (gemm_shortk.hip)
 int launch_gemm_shortk(const GemmArgs& g, hipStream_t st);      // ... bit-identical to launch_gemm_sf16, every wave MFMA + neurons
-int launch_gemm_split_rows(const GemmArgs& g, hipStream_t st, bool allow_bt = true);  // picks between the two (model.hip; allow_bt = false: ring only)
+// A in split rows, W pre-split: big-tile where allowed and gemm_sf16_bt_ok, else ring — as routed by gemm_route (model.hip), which
+// states the order of all five launchers above
+int launch_gemm_split_rows(const GemmArgs& g, hipStream_t st, bool allow_bt = true);
 int launch_split_weights(const float* w, int64_t count, void* hi, void* lo, int* ovf, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------

@@ -467,7 +467,7 @@ bool gemm_sf16_bt_ok(const GemmArgs& g) {
     if (((uintptr_t)g.a & 15) || ((uintptr_t)g.w16_hi & 15) || ((uintptr_t)g.w16_lo & 15)) return false;
     if (g.n % 128) return false;
     if (4 * (int64_t)g.lda * TBM >= (1LL << 31)) return false;        // 32-bit per-lane DMA offsets inside a tile
-    if (g.r < 4 * TBM) return false;                                   // small launches: the 128x128 tiles fill the chip better
+    if (g.r < 4 * TBM) return false;       // small launches: the 128x128 tiles fill the chip better (r == 0 too: the ring launcher's no-op)
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };       // the row-layout epilogue works on float4s
     if (g.ldc % 4 || !al16(g.c) || (g.bias && !al16(g.bias))) return false;
     if ((g.epi == EPI_LIF || g.epi == EPI_LIF_ATTN) && !al16(g.lif)) return false;

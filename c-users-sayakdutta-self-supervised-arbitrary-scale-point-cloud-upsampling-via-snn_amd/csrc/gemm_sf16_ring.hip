@@ -427,15 +427,27 @@ template <int EPI>
 static int launch_ring_t(const GemmArgs& g, hipStream_t st) {
     return ring_vec_ok(g) ? launch_ring_tv<EPI, true, true>(g, st) : launch_ring_tv<EPI, false, true>(g, st);
 }
+// Does this kernel take the call?  An empty one (r == 0 or n == 0) is taken whatever its operands: nothing is launched.  *why: the text
+// of a refusal.  The router (gemm_route, model.hip) asks this once the big-tile kernel has declined a split-row GEMM.
+bool gemm_sf16_ring_accepts(const GemmArgs& g, const char** why) {
+    const bool lif = g.epi == EPI_LIF || g.epi == EPI_LIF_ATTN, resid = g.epi == EPI_RESID || g.epi == EPI_RESID_GELU;
+    *why = nullptr;
+    if (g.r == 0 || g.n == 0) return true;
+    if (!g.a_split) *why = "gemm_ring: A must be in split rows";
+    else if (g.k <= 0 || g.k % RBK || g.k > g.lda) *why = "gemm_ring: k must be a positive multiple of 32 and <= lda";
+    else if (g.lda % 8 || !g.w16_hi || !g.w16_lo || (((uintptr_t)g.a | (uintptr_t)g.w16_hi | (uintptr_t)g.w16_lo) & 15))
+        *why = "gemm_ring: operands must be 16-byte aligned with lda % 8 == 0";
+    else if (lif && !g.lif) *why = "gemm_ring: missing neuron parameters";
+    else if (resid && !g.resid) *why = "gemm_ring: missing residual";
+    else if (g.epi == EPI_LIF_ATTN && !(g.ldq > 0 && g.tab && g.q && g.kf && g.c2)) *why = "gemm_ring: bad attn operands";
+    else if (!lif && !resid && g.epi != EPI_BIAS && g.epi != EPI_GELU && g.epi != EPI_LRELU) *why = "gemm_ring: epilogue not served";
+    return *why == nullptr;
+}
+
 int launch_gemm_sf16_ring(const GemmArgs& g, hipStream_t st) {
+    const char* why;
+    SAPCU_CHECK_ARG(gemm_sf16_ring_accepts(g, &why), "%s", why);
     if (g.r == 0 || g.n == 0) return SAPCU_OK;
-    SAPCU_CHECK_ARG(g.a_split, "gemm_ring: A must be in split rows");
-    SAPCU_CHECK_ARG(g.k > 0 && g.k % RBK == 0 && g.k <= g.lda, "gemm_ring: k=%d must be a multiple of %d and <= lda", g.k, RBK);
-    SAPCU_CHECK_ARG(g.lda % 8 == 0 && ((uintptr_t)g.a & 15) == 0 && g.w16_hi && g.w16_lo &&
-                        ((uintptr_t)g.w16_hi & 15) == 0 && ((uintptr_t)g.w16_lo & 15) == 0,
-                    "gemm_ring: operands must be 16-byte aligned with lda %% 8 == 0 (lda=%d)", g.lda);
-    if (g.epi == EPI_LIF || g.epi == EPI_LIF_ATTN) SAPCU_CHECK_ARG(g.lif, "gemm_ring: missing neuron parameters");
-    if (g.epi == EPI_RESID || g.epi == EPI_RESID_GELU) SAPCU_CHECK_ARG(g.resid, "gemm_ring: missing residual");
     switch (g.epi) {
         case EPI_BIAS: return launch_ring_t<EPI_BIAS>(g, st);
         case EPI_LIF: return launch_ring_t<EPI_LIF>(g, st);
@@ -443,10 +455,7 @@ int launch_gemm_sf16_ring(const GemmArgs& g, hipStream_t st) {
         case EPI_RESID: return launch_ring_t<EPI_RESID>(g, st);
         case EPI_LRELU: return launch_ring_t<EPI_LRELU>(g, st);
         case EPI_RESID_GELU: return launch_ring_t<EPI_RESID_GELU>(g, st);
-        case EPI_LIF_ATTN:
-            SAPCU_CHECK_ARG(g.ldq > 0 && g.tab && g.q && g.kf && g.c2, "gemm_ring: bad attn operands");
-            return launch_ring_t<EPI_LIF_ATTN>(g, st);
-        default: set_error("gemm_ring: unknown epilogue %d", g.epi); return SAPCU_ERR_ARG;
+        default: return launch_ring_t<EPI_LIF_ATTN>(g, st);
     }
 }
 

@@ -5,7 +5,8 @@
 // fd_ws_layout: sapcu_workspace_bytes is that function on a null base, the forward carves the caller's buffer with it.
 //  * In split-f16 mode (the default; SAPCU_GEMM=f32 or a weight outside the f16 range falls back to the exact-f32 MFMA GEMM) the 1x1
 //    convolutions / Linears run as 3 x f16 MFMA GEMMs on weights split once at model build, neuron loops fused as epilogues; tensors
-//    that only feed another GEMM travel as split rows.
+//    that only feed another GEMM travel as split rows.  Every GEMM, a handle's or a raw entry point's, is a descriptor filled by the
+//    Gemm builder and sent through gemm_route, the one place that says which of the five GEMM kernels a descriptor reaches.
 //  * fn: per block fc1 and q|k|v GEMMs over all rows of the chunk, then the edge chain — ONE kernel with the activations in LDS
 //    (fn_edge_chain.hip) for the shapes it takes, else five kernels over [rows * k, d] tensors in HBM — and out_proj . fc2 folded
 //    into one GEMM at model build.
@@ -15,6 +16,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -127,15 +129,91 @@ namespace sapcu {
 static inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
 static inline int imin(int a, int b) { return a < b ? a : b; }
 
-// GEMM on split rows: the big-tile kernel for the shapes it takes (allow_bt = false — a handle created under SAPCU_BT=0, or a raw
-// entry point asked for the ring kernel — keeps everything on the ring kernel; the two are bit-identical), else the 128x128
-// ring kernel.
-static bool split_rows_gemm_on_big_tile(const GemmArgs& g, bool allow_bt) { return allow_bt && gemm_sf16_bt_ok(g); }
+#define SAPCU_TRY(expr)                 \
+    do {                                \
+        int _rc = (expr);               \
+        if (_rc != SAPCU_OK) return _rc; \
+    } while (0)
 
-int launch_gemm_split_rows(const GemmArgs& g, hipStream_t st, bool allow_bt) {
-    if (split_rows_gemm_on_big_tile(g, allow_bt)) return launch_gemm_sf16_bt(g, st);
-    return launch_gemm_sf16_ring(g, st);
+// ---------------------------------------------------------------- the GEMM router
+// Which launcher a filled descriptor reaches: the ONLY statement of the order (the _ok / _accepts predicates stay with their kernels).
+//   have16        split weights are attached (g.w16_hi / w16_lo).  Handle: split-f16 mode and g.w inside the handle's blob; raw entry
+//                 points: the caller gave a w16_ws scratch.
+//   allow_bt      handle: not created under SAPCU_BT=0; raw: a_split_rows / split_rows != 2.
+//   allow_shortk  handle: not created under SAPCU_SHORTK=0; raw sapcu_gemm_f32: SAPCU_SHORTK read at the call.  The posenc GEMM cannot get
+//                 there whatever it passes: gemm_shortk_ok refuses EPI_LIF_ATTN.
+// The first row that applies decides:
+//   have16  a_split  allow_bt && gemm_sf16_bt_ok                    big tile
+//   have16  a_split  gemm_sf16_ring_accepts                         ring (every r == 0 call ends here: SAPCU_OK without a launch)
+//   have16  a_split                                                 refused, the ring's text
+//   have16           allow_shortk && gemm_shortk_ok                 short K
+//   have16           max_out                                        refused: "a direct max output needs the short-K kernel"
+//   have16           k % 64 == 0                                    f32 A, split per tile (its K step is 64)
+//   have16           c_split | c2_split                             refused: "split-row output needs k % 64 == 0 on the f32-A path"
+//           a_split | c_split | c2_split                            refused: "split-row operands need the split-f16 kernels"
+//                                                                   exact f32
+typedef int (*GemmLauncher)(const GemmArgs&, hipStream_t);
+
+// the launcher, or null with the refusal's text in *why; launches and writes nothing, sets no error
+static GemmLauncher gemm_route(const GemmArgs& g, bool have16, bool allow_bt, bool allow_shortk, const char** why) {
+    if (have16 && g.a_split) {
+        if (allow_bt && gemm_sf16_bt_ok(g)) return launch_gemm_sf16_bt;
+        return gemm_sf16_ring_accepts(g, why) ? launch_gemm_sf16_ring : nullptr;
+    }
+    *why = nullptr;
+    if (have16) {
+        if (allow_shortk && gemm_shortk_ok(g)) return launch_gemm_shortk;
+        if (g.max_out) *why = "run_gemm: a direct max output needs the short-K kernel";
+        else if (g.k % 64 == 0) return launch_gemm_sf16;
+        else if (g.c_split || g.c2_split) *why = "gemm: split-row output needs k % 64 == 0 on the f32-A path";
+    } else if (g.a_split || g.c_split || g.c2_split) {
+        *why = "run_gemm: split-row operands need the split-f16 kernels";
+    }
+    return *why ? nullptr : launch_gemm;
 }
+
+// A raw entry point's split scratch for cnt weights: hi (2 cnt B) | lo (2 cnt B) | overflow counter
+struct SplitWs {
+    _Float16 *hi, *lo;
+    int* ovf;
+    int64_t cnt;
+    SplitWs(void* ws, int64_t cnt_) : hi((_Float16*)ws), lo(hi + cnt_), ovf((int*)(lo + cnt_)), cnt(cnt_) {}
+    void attach(GemmArgs& g) const { g.w16_hi = hi; g.w16_lo = lo; g.ovf = ovf; }      // pointers only: nothing is written
+    int fill(const float* w, hipStream_t st) const {                                    // zero the counter, split w into the planes
+        SAPCU_CHECK_HIP(hipMemsetAsync(ovf, 0, sizeof(int), st));
+        return launch_split_weights(w, cnt, hi, lo, ovf, st);
+    }
+};
+
+// Route and launch; a refusal becomes the thread's error text before anything is launched or written.  raw: the scratch attached to g,
+// filled between the two steps — the exact-f32 route leaves it untouched.
+static int gemm_run(const GemmArgs& g, bool have16, bool allow_bt, bool allow_shortk, hipStream_t st, const SplitWs* raw = nullptr) {
+    const char* why = nullptr;
+    const GemmLauncher run = gemm_route(g, have16, allow_bt, allow_shortk, &why);
+    SAPCU_CHECK_ARG(run, "%s", why);
+    if (raw && run != launch_gemm) SAPCU_TRY(raw->fill(g.w, st));
+    return run(g, st);
+}
+
+int launch_gemm_split_rows(const GemmArgs& g, hipStream_t st, bool allow_bt) { return gemm_run(g, true, allow_bt, false, st); }
+
+// A descriptor under construction: the ten fields every GEMM has, then one named setter per group an epilogue or a format adds.  The
+// rest stays zero; GemmArgs itself (what the kernels take by value) is untouched.
+struct Gemm : GemmArgs {
+    Gemm(const float* a_, int64_t r_, int k_, int lda_, const float* w_, int n_, const float* bias_, float* c_, int ldc_, int epi_)
+        : GemmArgs{} {
+        a = a_; r = r_; k = k_; lda = lda_; w = w_; n = n_; bias = bias_; c = c_; ldc = ldc_; epi = epi_;
+    }
+    Gemm& neuron(const float* params, int steps) { lif = params; lif_T = steps; return *this; }
+    Gemm& residual(const float* x, int ld) { resid = x; ldr = ld; return *this; }
+    Gemm& split_in(int on = 1) { a_split = on; return *this; }
+    Gemm& split_out(int on = 1) { c_split = on; return *this; }
+    Gemm& split_out2(int on = 1) { c2_split = on; return *this; }
+    // EPI_LIF_ATTN: c2 = q[tab.x] - kf[tab.y] + c, q | kf the first two d-column groups of qkv rows [*, 3 d]
+    Gemm& attn(float* c2_, const float* qkv, int d, const int2* tab_) { c2 = c2_; q = qkv; kf = qkv + d; ldq = 3 * d; tab = tab_; return *this; }
+    // EPI_*_MAX: keys of the max over groups of m rows; out: the float maxima written directly (short-K kernel, whole patches per row group)
+    Gemm& max_rows(unsigned* keys, int m, float* out = nullptr) { max_keys = keys; max_m = m; max_out = out; return *this; }
+};
 
 // out_proj followed by fc2 (two affine maps with nothing between them, fn/snn_coder.py:393-394) as one: w_fold [n, d] = w2 . w1 and
 // b_fold [n] = w2 . b1 + b2 for w1 [d, d], b1 [d] (out_proj) and w2 [n, d], b2 [n] (fc2), BatchNorm already folded.  HOST pointers;
@@ -196,52 +274,41 @@ static void free_model(sapcu_model* m) {
     delete m;
 }
 
-// Route a GEMM to the split-f16 kernel when the model carries pre-split weights, else to the f32 MFMA kernel.
-static int run_gemm(const sapcu_model* m, GemmArgs& g, hipStream_t st) {
-    const bool have16 = m && m->sf16 && g.w >= m->blob && g.w < m->blob + m->blob_floats;
-    if (have16) {
-        const int64_t off = g.w - m->blob;
-        g.w16_hi = (const _Float16*)m->w16_hi + off;
-        g.w16_lo = (const _Float16*)m->w16_lo + off;
-        g.ovf = m->ovf_dev;
-        if (g.a_split) return launch_gemm_split_rows(g, st, m->opt_bt);   // A already split by its producer: all-DMA kernels
-        if (m->opt_shortk && gemm_shortk_ok(g)) return launch_gemm_shortk(g, st);   // short K, neuron epilogue: every wave does both
-        if (g.max_out) {
-            set_error("run_gemm: a direct max output needs the short-K kernel");
-            return SAPCU_ERR_ARG;
-        }
-        if (g.k % 64 == 0) return launch_gemm_sf16(g, st);
-    }
-    if (g.a_split || g.c_split || g.c2_split) {
-        set_error("run_gemm: split-row operands need the split-f16 kernels");
-        return SAPCU_ERR_ARG;
-    }
-    return launch_gemm(g, st);
+// The handle's split planes and overflow counter attached to a descriptor whose weights are the handle's (split-f16 mode); says
+// whether it did.  Anything else runs on exact f32.
+static bool attach_split_weights(const sapcu_model* m, GemmArgs& g) {
+    if (!m->sf16 || g.w < m->blob || g.w >= m->blob + m->blob_floats) return false;
+    const int64_t off = g.w - m->blob;
+    g.w16_hi = (const _Float16*)m->w16_hi + off;
+    g.w16_lo = (const _Float16*)m->w16_lo + off;
+    g.ovf = m->ovf_dev;
+    return true;
 }
 
-// fmt bit 0: A is in split rows; bit 1: write C in split rows (both only in split-f16 mode)
-static int gemm(const sapcu_model* m, const float* a, int64_t r, int k, int lda, const float* w, int n,
-                const float* bias, float* c, int ldc, int epi, hipStream_t st, const float* lif = nullptr,
-                int lifT = 0, const float* resid = nullptr, int ldr = 0, int fmt = 0) {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.r = r; g.k = k; g.lda = lda; g.w = w; g.n = n; g.bias = bias; g.c = c; g.ldc = ldc;
-    g.epi = epi; g.lif = lif; g.lif_T = lifT; g.resid = resid; g.ldr = ldr;
-    g.a_split = fmt & 1; g.c_split = (fmt >> 1) & 1;
-    return run_gemm(m, g, st);
+static int run_gemm(const sapcu_model* m, GemmArgs g, hipStream_t st) {
+    const bool have16 = attach_split_weights(m, g);
+    return gemm_run(g, have16, m->opt_bt, m->opt_shortk, st);
 }
-
-#define SAPCU_TRY(expr)                 \
-    do {                                \
-        int _rc = (expr);               \
-        if (_rc != SAPCU_OK) return _rc; \
-    } while (0)
 
 static int tap_copy(void* const* taps, int which, int64_t dst_off_bytes, const void* src, int64_t bytes,
                     hipStream_t st) {
     if (!taps || !taps[which] || bytes == 0) return SAPCU_OK;
     SAPCU_CHECK_HIP(hipMemcpyAsync((char*)taps[which] + dst_off_bytes, src, (size_t)bytes, hipMemcpyDeviceToDevice, st));
     return SAPCU_OK;
+}
+
+// a [T][cb] tensor of `row` floats per patch into its tap, laid out [T][b]: this chunk's patches [s, s + cb) of every step
+static int tap_copy_steps(void* const* taps, int which, int T, int64_t b, int64_t s, int64_t cb, int64_t row, const float* src,
+                          hipStream_t st) {
+    for (int t = 0; t < T; ++t) SAPCU_TRY(tap_copy(taps, which, ((int64_t)t * b + s) * row * 4, src + (int64_t)t * cb * row, cb * row * 4, st));
+    return SAPCU_OK;
+}
+
+// the caller's workspace against a layout's bytes + the 256 the align-up of its pointer may cost
+static int check_workspace(const char* who, int64_t ws_bytes, size_t layout_bytes) {
+    if (ws_bytes >= (int64_t)layout_bytes + 256) return SAPCU_OK;
+    set_error("%s: workspace %lld B < required %lld B", who, (long long)ws_bytes, (long long)layout_bytes + 256);
+    return SAPCU_ERR_WORKSPACE;
 }
 
 // ============================================================================ fn
@@ -369,8 +436,7 @@ struct FnEdge {
 // the whole edge chain in one kernel, activations in LDS (fn_edge_chain.hip)      fn:355-389
 static int fn_edge_chain_fused(const sapcu_model* m, const FnWs& W, const FnEdge& e, hipStream_t st) {
     const int d = e.d, sb = e.sb;
-    ChainArgs ca;
-    memset(&ca, 0, sizeof(ca));
+    ChainArgs ca{};
     ca.P = e.P; ca.m = e.mp; ca.qkv = W.QKV; ca.ldq = 3 * d;
     ca.wd = m->p(sb + B_DELTA_W); ca.bd = m->p(sb + B_DELTA_B); ca.lifd = m->p(sb + B_DELTA_LIF);
     const _Float16* cw = (const _Float16*)m->chain_w;
@@ -402,22 +468,14 @@ static int fn_edge_chain_unfused(const sapcu_model* m, const FnWs& W, const FnEd
     SAPCU_TRY(launch_fn_pe1(e.pc, idx, R, e.mp, kk, d, m->p(sb + B_DELTA_W), m->p(sb + B_DELTA_B), m->p(sb + B_DELTA_LIF), 4, W.B1, SP,
                             st));
     // pe = LIF(fc_delta2(pe1)) -> B2, and in the same epilogue attn_in = q_i - k_j + pe -> B3   fn:360-368
-    {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.a = W.B1; g.r = R; g.k = d; g.lda = d; g.w = m->p(sb + B_DELTA2_W); g.n = d;
-        g.bias = m->p(sb + B_DELTA2_B); g.c = W.B2; g.ldc = d; g.epi = EPI_LIF_ATTN;
-        g.lif = m->p(sb + B_DELTA2_LIF); g.lif_T = 4; g.c2 = W.B3;
-        g.q = W.QKV; g.kf = W.QKV + d; g.ldq = 3 * d; g.tab = W.tab;
-        g.a_split = SP; g.c2_split = SP;
-        SAPCU_TRY(launch_edge_table(idx, R, e.mp, kk, W.tab, st));
-        SAPCU_TRY(run_gemm(m, g, st));
-    }
+    SAPCU_TRY(launch_edge_table(idx, R, e.mp, kk, W.tab, st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.B1, R, d, d, m->p(sb + B_DELTA2_W), d, m->p(sb + B_DELTA2_B), W.B2, d, EPI_LIF_ATTN)
+                              .neuron(m->p(sb + B_DELTA2_LIF), 4).attn(W.B3, W.QKV, d, W.tab).split_in(SP).split_out2(SP), st));
     // g = LIF(fc_gamma(attn_in)) -> B1                                      fn:373-376
-    SAPCU_TRY(gemm(m, W.B3, R, d, d, m->p(sb + B_GAMMA_W), d, m->p(sb + B_GAMMA_B), W.B1, d, EPI_LIF, st, m->p(sb + B_GAMMA_LIF), 4,
-                   nullptr, 0, SP | (SP << 1)));
+    SAPCU_TRY(run_gemm(m, Gemm(W.B3, R, d, d, m->p(sb + B_GAMMA_W), d, m->p(sb + B_GAMMA_B), W.B1, d, EPI_LIF)
+                              .neuron(m->p(sb + B_GAMMA_LIF), 4).split_in(SP).split_out(SP), st));
     // a = fc_gamma2(g) -> B3                                                fn:378
-    SAPCU_TRY(gemm(m, W.B1, R, d, d, m->p(sb + B_GAMMA2_W), d, m->p(sb + B_GAMMA2_B), W.B3, d, EPI_BIAS, st, nullptr, 0, nullptr, 0, SP));
+    SAPCU_TRY(run_gemm(m, Gemm(W.B1, R, d, d, m->p(sb + B_GAMMA2_W), d, m->p(sb + B_GAMMA2_B), W.B3, d, EPI_BIAS).split_in(SP), st));
     // res = sum_j softmax_j(a / sqrt(hd)) * (v_j + pe)                      fn:379-389
     return launch_fn_softmax_agg(W.B3, W.B2, W.QKV + 2 * d, 3 * d, idx, e.P, e.mp, kk, d, e.sqrt_hd, W.RES, SP, st);
 }
@@ -427,10 +485,7 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
                       hipStream_t st) {
     const FnPlan pl = fn_plan(m, b, mp);
     const FnWs W = fn_ws_layout(ws_align256(ws), m, pl, mp);
-    if (ws_bytes < (int64_t)W.bytes + 256) {
-        set_error("fn_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)W.bytes + 256);
-        return SAPCU_ERR_WORKSPACE;
-    }
+    SAPCU_TRY(check_workspace("fn_forward", ws_bytes, W.bytes));
     // offsets of the three tables inside knn_in / knn_out ([b,m,k0] | [b,m,k1] | [b,m,k2])
     int64_t tab_off[3];
     tab_off[0] = 0;
@@ -467,23 +522,23 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
             const int SP = m->sf16 ? 1 : 0;
             float* const out = W.cat + 64 * l;             // the block's 64 output columns
             // x = LIF(fc1(feat))                                                    fn:317-320
-            SAPCU_TRY(gemm(m, fin, P, 64, ldin, m->p(sb + B_FC1_W), d, m->p(sb + B_FC1_B), W.X, d, EPI_LIF, st,
-                           m->p(sb + B_SNN1), 4, nullptr, 0, SP << 1));
+            SAPCU_TRY(run_gemm(m, Gemm(fin, P, 64, ldin, m->p(sb + B_FC1_W), d, m->p(sb + B_FC1_B), W.X, d, EPI_LIF)
+                                      .neuron(m->p(sb + B_SNN1), 4).split_out(SP), st));
             // q|k|v = LIF(w_qs|w_ks|w_vs (x))                                       fn:322-335
-            SAPCU_TRY(gemm(m, W.X, P, d, d, m->p(sb + B_QKV_W), 3 * d, m->p(sb + B_QKV_B), W.QKV, 3 * d, EPI_LIF, st,
-                           m->p(sb + B_QKV_LIF), 4, nullptr, 0, SP));
+            SAPCU_TRY(run_gemm(m, Gemm(W.X, P, d, d, m->p(sb + B_QKV_W), 3 * d, m->p(sb + B_QKV_B), W.QKV, 3 * d, EPI_LIF)
+                                      .neuron(m->p(sb + B_QKV_LIF), 4).split_in(SP), st));
             const FnEdge e{pc, P, mp, l, d, pl.kk[l], sb, SP, (float)sqrt((double)(d / m->heads)), pl.edge_floats};
             SAPCU_TRY(fn_block_fused(m, l, mp) ? fn_edge_chain_fused(m, W, e, st) : fn_edge_chain_unfused(m, W, e, st));
             // out_proj, fc2 + residual                                              fn:393-394
             if (m->opt_fn_fold_out) {
                 // the two layers folded into one at model build (fold_w / fold_b): res goes straight to the block's 64 output columns
-                SAPCU_TRY(gemm(m, W.RES, P, d, d, m->blob + m->fold_w[l], 64, m->blob + m->fold_b[l], out, 192, EPI_RESID, st,
-                               nullptr, 0, fin, ldin, SP));
+                SAPCU_TRY(run_gemm(m, Gemm(W.RES, P, d, d, m->blob + m->fold_w[l], 64, m->blob + m->fold_b[l], out, 192, EPI_RESID)
+                                          .residual(fin, ldin).split_in(SP), st));
             } else {
-                SAPCU_TRY(gemm(m, W.RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), W.X, d, EPI_BIAS, st, nullptr, 0, nullptr,
-                               0, SP | (SP << 1)));
-                SAPCU_TRY(gemm(m, W.X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), out, 192, EPI_RESID, st,
-                               nullptr, 0, fin, ldin, SP));
+                SAPCU_TRY(run_gemm(m, Gemm(W.RES, P, d, d, m->p(sb + B_OUT_W), d, m->p(sb + B_OUT_B), W.X, d, EPI_BIAS)
+                                          .split_in(SP).split_out(SP), st));
+                SAPCU_TRY(run_gemm(m, Gemm(W.X, P, d, d, m->p(sb + B_FC2_W), 64, m->p(sb + B_FC2_B), out, 192, EPI_RESID)
+                                          .residual(fin, ldin).split_in(SP), st));
             }
             if (taps && taps[SAPCU_FN_TAP_BLOCK1 + l]) {
                 SAPCU_CHECK_HIP(hipMemcpy2DAsync((char*)taps[SAPCU_FN_TAP_BLOCK1 + l] + s * mp * 64 * 4, 64 * 4,
@@ -496,29 +551,25 @@ static int fn_forward(const sapcu_model* m, const float* patch, int64_t b, int m
         if (m->sf16 && m->opt_fn_maxfuse) {
             // the max over the patch's points inside the GEMM's epilogue (integer atomicMax on order-preserving keys, as fd's
             // multi_scale_conv): the [P, emb] activation is never written.  Keys live at the head of the unused B1 area.
-            GemmArgs g;
-            memset(&g, 0, sizeof(g));
-            g.a = W.cat; g.r = P; g.k = 192; g.lda = 192; g.w = m->p(FN_FINAL_W); g.n = m->emb; g.bias = m->p(FN_FINAL_B);
-            g.ldc = m->emb; g.epi = EPI_LIF_MAX; g.lif = m->p(FN_FINAL_LIF); g.lif_T = m->T;
-            g.max_keys = reinterpret_cast<unsigned*>(W.B1); g.max_m = mp;
+            unsigned* const keys = reinterpret_cast<unsigned*>(W.B1);
             // whole patches per row group (M = 48): gemm_shortk.hip takes the max in registers and writes pooled itself
             const bool direct = m->opt_shortk && mp == 48;
-            if (direct) g.max_out = W.pooled;
-            else SAPCU_CHECK_HIP(hipMemsetAsync(g.max_keys, 0, (size_t)cb * m->emb * 4, st));
-            SAPCU_TRY(run_gemm(m, g, st));
-            if (!direct) SAPCU_TRY(launch_decode_max_keys(g.max_keys, cb * m->emb, W.pooled, st));
+            if (!direct) SAPCU_CHECK_HIP(hipMemsetAsync(keys, 0, (size_t)cb * m->emb * 4, st));
+            SAPCU_TRY(run_gemm(m, Gemm(W.cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), nullptr, m->emb, EPI_LIF_MAX)
+                                      .neuron(m->p(FN_FINAL_LIF), m->T).max_rows(keys, mp, direct ? W.pooled : nullptr), st));
+            if (!direct) SAPCU_TRY(launch_decode_max_keys(keys, cb * m->emb, W.pooled, st));
         } else {
-            SAPCU_TRY(gemm(m, W.cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), W.B1, m->emb, EPI_LIF, st,
-                           m->p(FN_FINAL_LIF), m->T));
+            SAPCU_TRY(run_gemm(m, Gemm(W.cat, P, 192, 192, m->p(FN_FINAL_W), m->emb, m->p(FN_FINAL_B), W.B1, m->emb, EPI_LIF)
+                                      .neuron(m->p(FN_FINAL_LIF), m->T), st));
             SAPCU_TRY(launch_rowgroup_max(W.B1, cb, mp, m->emb, W.pooled, st));
         }
         SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_POOLED, s * m->emb * 4, W.pooled, cb * m->emb * 4, st));
-        SAPCU_TRY(gemm(m, W.pooled, cb, m->emb, m->emb, m->p(FN_FCOUT_W), 2048, m->p(FN_FCOUT_B), W.enc, 2048, EPI_BIAS, st));
+        SAPCU_TRY(run_gemm(m, Gemm(W.pooled, cb, m->emb, m->emb, m->p(FN_FCOUT_W), 2048, m->p(FN_FCOUT_B), W.enc, 2048, EPI_BIAS), st));
         SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_ENC, s * 2048 * 4, W.enc, cb * 2048 * 4, st));
         // decoder MLP (Linear+BN+GELU) x3, Linear(256,3), LayerNorm(3), normalize    fn:542-549
-        SAPCU_TRY(gemm(m, W.enc, cb, 2048, 2048, m->p(FN_MLP0_W), 1024, m->p(FN_MLP0_B), W.h1, 1024, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, W.h1, cb, 1024, 1024, m->p(FN_MLP1_W), 512, m->p(FN_MLP1_B), W.h2, 512, EPI_GELU, st));
-        SAPCU_TRY(gemm(m, W.h2, cb, 512, 512, m->p(FN_MLP2_W), 256, m->p(FN_MLP2_B), W.h3, 256, EPI_GELU, st));
+        SAPCU_TRY(run_gemm(m, Gemm(W.enc, cb, 2048, 2048, m->p(FN_MLP0_W), 1024, m->p(FN_MLP0_B), W.h1, 1024, EPI_GELU), st));
+        SAPCU_TRY(run_gemm(m, Gemm(W.h1, cb, 1024, 1024, m->p(FN_MLP1_W), 512, m->p(FN_MLP1_B), W.h2, 512, EPI_GELU), st));
+        SAPCU_TRY(run_gemm(m, Gemm(W.h2, cb, 512, 512, m->p(FN_MLP2_W), 256, m->p(FN_MLP2_B), W.h3, 256, EPI_GELU), st));
         SAPCU_TRY(launch_fn_tail(W.h3, cb, 256, m->p(FN_HEAD_W), m->p(FN_HEAD_B), m->p(FN_LN_W), m->p(FN_LN_B), W.logits,
                                  normals + s * 3, st));
         SAPCU_TRY(tap_copy(taps, SAPCU_FN_TAP_LOGITS, s * 3 * 4, W.logits, cb * 3 * 4, st));
@@ -638,8 +689,7 @@ static const int FD_CIN[4] = {0, 64, 128, 256}, FD_COUT[4] = {64, 128, 256, 512}
 
 // the whole encoder up to pooled [T, cb, emb] in ONE launch, one workgroup per patch (fd_encoder.hip)   fd:408-480
 static int fd_encode_fused(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const FdChunk& c, hipStream_t st) {
-    FdEncArgs ea;
-    memset(&ea, 0, sizeof(ea));
+    FdEncArgs ea{};
     ea.patch = c.pc; ea.b = c.cb; ea.b_total = c.b; ea.s0 = c.s;
     ea.m = c.mp; ea.T = m->T; ea.kk = pl.kk; ea.kmax0 = pl.kmax0; ea.nscale = m->nscale; ea.emb = m->emb;
     for (int i = 0; i < 4; ++i) ea.ks[i] = i < m->nscale ? imin(m->ks[i], c.mp) : 0;
@@ -663,12 +713,9 @@ static int fd_encode_fused(const sapcu_model* m, const FdPlan& pl, const FdWs& W
 }
 
 // multi_scale_conv as a GEMM over the T spike slabs with the max over the points in its epilogue (keys at the head of AGG)
-static GemmArgs fd_msc_gemm_args(const sapcu_model* m, const FdWs& W, const FdChunk& c) {
-    GemmArgs mg;
-    memset(&mg, 0, sizeof(mg));
-    mg.a = W.SPK; mg.r = (int64_t)m->T * c.P(); mg.k = 960; mg.lda = 960; mg.w = m->p(FD_MSC_W); mg.n = m->emb; mg.bias = m->p(FD_MSC_B);
-    mg.c = nullptr; mg.ldc = m->emb; mg.epi = EPI_LRELU_MAX; mg.max_keys = reinterpret_cast<unsigned*>(W.AGG); mg.max_m = c.mp;
-    return mg;
+static Gemm fd_msc_gemm(const sapcu_model* m, const FdWs& W, const FdChunk& c, bool split_spikes) {
+    return Gemm(W.SPK, (int64_t)m->T * c.P(), 960, 960, m->p(FD_MSC_W), m->emb, m->p(FD_MSC_B), nullptr, m->emb, EPI_LRELU_MAX)
+        .max_rows(reinterpret_cast<unsigned*>(W.AGG), c.mp).split_in(split_spikes);
 }
 
 // The per-stage front: block 0 (xyz kNN, EdgeConv x S, scale fusion, EIF over T steps, fd:411-444) and blocks 1..3 (feature-space
@@ -681,7 +728,7 @@ static int fd_front(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const
     // all scales are prefixes of the sorted top-kmax list
     SAPCU_TRY(launch_patch_knn(c.pc, cb, mp, 3, 3, pl.kmax0, W.idx0, st));
     SAPCU_TRY(launch_fd_edge0(c.pc, W.idx0, pl.kmax0, P, mp, m->nscale, m->ks_dev, m->p(FD_E0_W), m->p(FD_E0_B), W.E0, st));
-    SAPCU_TRY(gemm(m, W.E0, P, 64 * m->nscale, 64 * m->nscale, m->p(FD_FUSE_W), 64, m->p(FD_FUSE_B), W.FUSED, 64, EPI_LRELU, st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.E0, P, 64 * m->nscale, 64 * m->nscale, m->p(FD_FUSE_W), 64, m->p(FD_FUSE_B), W.FUSED, 64, EPI_LRELU), st));
     SAPCU_TRY(tap_copy(taps, SAPCU_FD_TAP_FUSED0, s * mp * 64 * 4, W.FUSED, P * 64 * 4, st));
     float* const X0T = c.x0_tap();
     if (X0T) SAPCU_CHECK_HIP(hipMemcpy2DAsync(X0T, 960 * 4, W.FUSED, 64 * 4, 64 * 4, (size_t)P, hipMemcpyDeviceToDevice, st));
@@ -691,11 +738,10 @@ static int fd_front(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const
     // SAPCU_GEMM=f32, SAPCU_FD_MAXFUSE=0 / SAPCU_FD_SPLIT=0, or a caller asking for the spike tap): f32 spikes for all steps.
     split_spikes = pl.x0path;                               // x0 path: ONE slab of step-0 split rows (the EdgeConv GEMMs' operand)
     if (!pl.x0path && pl.maxfuse && m->opt_fd_split && !c.tap(SAPCU_FD_TAP_SPIKES)) {
-        GemmArgs probe = fd_msc_gemm_args(m, W, c);
-        probe.a_split = 1;
-        probe.w16_hi = (const _Float16*)m->w16_hi + (probe.w - m->blob);
-        probe.w16_lo = (const _Float16*)m->w16_lo + (probe.w - m->blob);
-        split_spikes = split_rows_gemm_on_big_tile(probe, m->opt_bt);     // (the ring kernel has no max-over-rows epilogue)
+        GemmArgs g = fd_msc_gemm(m, W, c, true);
+        const char* why;
+        const bool have16 = attach_split_weights(m, g);
+        split_spikes = gemm_route(g, have16, m->opt_bt, m->opt_shortk, &why) == launch_gemm_sf16_bt;     // (the ring kernel has no max-over-rows epilogue)
     }
     float* const SPKS = split_spikes ? W.SPK : nullptr;     // [T*P, 960] split rows (same buffer, other format)
     float* const SPK0 = split_spikes ? W.F0 : W.SPK;        // where the step-0 f32 spikes live ([P, 960] slab)
@@ -718,11 +764,8 @@ static int fd_front(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const
         const int ew = FD_EDGE1_W + 3 * (l - 1);
         // the factored EdgeConv's GEMM reads the step-0 spikes as split rows when the neuron kernels wrote them (rows 0..P-1 of
         // SPKS, same pitch and column offsets as the f32 slab): the all-DMA kernels instead of the f32-operand one, same sums
-        if (split_spikes)
-            SAPCU_TRY(gemm(m, SPKS + coff, P, cin, 960, m->p(ew), 2 * cout, nullptr, W.AB, 2 * cout, EPI_BIAS, st, nullptr, 0, nullptr, 0,
-                           1));
-        else
-            SAPCU_TRY(gemm(m, F, P, cin, 960, m->p(ew), 2 * cout, nullptr, W.AB, 2 * cout, EPI_BIAS, st));
+        SAPCU_TRY(run_gemm(m, Gemm(split_spikes ? SPKS + coff : F, P, cin, 960, m->p(ew), 2 * cout, nullptr, W.AB, 2 * cout, EPI_BIAS)
+                                  .split_in(split_spikes), st));
         SAPCU_TRY(launch_fd_neuron(l == 1, 1, W.AB, 2 * cout, idl, pl.kk, mp, m->p(ew + 1), P, cout, m->p(ew + 2), T, SPK0, 960,
                                    FD_COFF[l], nullptr, m->gate_dev, st, SPKS, X0P));
         if (X0T && !pl.x0path)
@@ -734,8 +777,7 @@ static int fd_front(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const
 // multi_scale_conv over all T steps + max over the points straight from x0: every spike regenerated on the CU (fd_msc_kernel)
 static int fd_msc_from_x0(const sapcu_model* m, const FdWs& W, const FdChunk& c, hipStream_t st) {
     if (c.x0_tap()) SAPCU_CHECK_HIP(hipMemcpyAsync(c.x0_tap(), W.X0, (size_t)c.P() * 960 * 4, hipMemcpyDeviceToDevice, st));
-    FdMscArgs ma;
-    memset(&ma, 0, sizeof(ma));
+    FdMscArgs ma{};
     ma.x0 = W.X0; ma.b = c.cb; ma.b_total = c.b; ma.s0 = c.s; ma.m = c.mp; ma.T = m->T; ma.emb = m->emb;
     ma.msc_wp = (const _Float16*)m->fde_w + m->fde_off[4]; ma.msc_b = m->p(FD_MSC_B); ma.nprm = m->fde_nprm;
     ma.pooled = W.POOLED; ma.tap_spikes = c.tap(SAPCU_FD_TAP_SPIKES); ma.gate = m->gate_dev;
@@ -746,21 +788,16 @@ static int fd_msc_from_x0(const sapcu_model* m, const FdWs& W, const FdChunk& c,
 static int fd_msc_from_slabs(const sapcu_model* m, const FdPlan& pl, const FdWs& W, const FdChunk& c, bool split_spikes, hipStream_t st) {
     const int T = m->T, emb = m->emb;
     const int64_t P = c.P();
-    if (c.tap(SAPCU_FD_TAP_SPIKES)) {
-        for (int t = 0; t < T; ++t)
-            SAPCU_CHECK_HIP(hipMemcpyAsync(c.tap(SAPCU_FD_TAP_SPIKES) + ((int64_t)t * c.b + c.s) * c.mp * 960,
-                                           W.SPK + (int64_t)t * P * 960, P * 960 * 4, hipMemcpyDeviceToDevice, st));
-    }
+    SAPCU_TRY(tap_copy_steps(c.taps, SAPCU_FD_TAP_SPIKES, T, c.b, c.s, c.cb, (int64_t)c.mp * 960, W.SPK, st));
     if (pl.maxfuse) {
         // the max over the patch's points inside the GEMM's epilogue (integer atomicMax on order-preserving keys): the
         // [T*P, emb] aggregate is never written.  The key buffer is the head of the (otherwise unused) AGG area.
-        GemmArgs mg = fd_msc_gemm_args(m, W, c);
+        const Gemm mg = fd_msc_gemm(m, W, c, split_spikes);
         SAPCU_CHECK_HIP(hipMemsetAsync(mg.max_keys, 0, (size_t)T * c.cb * emb * 4, st));
-        mg.a_split = split_spikes ? 1 : 0;
         SAPCU_TRY(run_gemm(m, mg, st));
         return launch_decode_max_keys(mg.max_keys, (int64_t)T * c.cb * emb, W.POOLED, st);
     }
-    SAPCU_TRY(gemm(m, W.SPK, (int64_t)T * P, 960, 960, m->p(FD_MSC_W), emb, m->p(FD_MSC_B), W.AGG, emb, EPI_LRELU, st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.SPK, (int64_t)T * P, 960, 960, m->p(FD_MSC_W), emb, m->p(FD_MSC_B), W.AGG, emb, EPI_LRELU), st));
     return launch_rowgroup_max(W.AGG, (int64_t)T * c.cb, c.mp, emb, W.POOLED, st);
 }
 
@@ -768,23 +805,19 @@ static int fd_msc_from_slabs(const sapcu_model* m, const FdPlan& pl, const FdWs&
 static int fd_temporal_decoder(const sapcu_model* m, const FdWs& W, const FdChunk& c, float* dist, hipStream_t st) {
     const int T = m->T, emb = m->emb;
     const int64_t cb = c.cb, s = c.s;
-    if (c.tap(SAPCU_FD_TAP_POOLED)) {
-        for (int t = 0; t < T; ++t)
-            SAPCU_CHECK_HIP(hipMemcpyAsync(c.tap(SAPCU_FD_TAP_POOLED) + ((int64_t)t * c.b + s) * emb, W.POOLED + (int64_t)t * cb * emb,
-                                           cb * emb * 4, hipMemcpyDeviceToDevice, st));
-    }
+    SAPCU_TRY(tap_copy_steps(c.taps, SAPCU_FD_TAP_POOLED, T, c.b, s, cb, emb, W.POOLED, st));
     SAPCU_TRY(launch_fd_temporal(W.POOLED, T, cb, emb, m->p(FD_TI_W), m->p(FD_SNNFC), W.ENC, st));
     SAPCU_TRY(tap_copy(c.taps, SAPCU_FD_TAP_ENC, s * emb * 4, W.ENC, cb * emb * 4, st));
     // decoder                                                                    fd:711-725
-    SAPCU_TRY(gemm(m, W.ENC, cb, emb, emb, m->p(FD_FCIN_W), 256, m->p(FD_FCIN_B), W.D1, 256, EPI_GELU, st));
-    SAPCU_TRY(gemm(m, W.D1, cb, 256, 256, m->p(FD_R0_FC0_W), 128, m->p(FD_R0_FC0_B), W.D2a, 128, EPI_GELU, st));
-    SAPCU_TRY(gemm(m, W.D1, cb, 256, 256, m->p(FD_R0_PROJ_W), 128, m->p(FD_R0_PROJ_B), W.D2b, 128, EPI_BIAS, st));
-    SAPCU_TRY(gemm(m, W.D2a, cb, 128, 128, m->p(FD_R0_FC4_W), 128, m->p(FD_R0_FC4_B), W.D2c, 128, EPI_RESID_GELU, st, nullptr, 0, W.D2b,
-                   128));
-    SAPCU_TRY(gemm(m, W.D2c, cb, 128, 128, m->p(FD_R1_FC0_W), 64, m->p(FD_R1_FC0_B), W.D3a, 64, EPI_GELU, st));
-    SAPCU_TRY(gemm(m, W.D2c, cb, 128, 128, m->p(FD_R1_PROJ_W), 64, m->p(FD_R1_PROJ_B), W.D3b, 64, EPI_BIAS, st));
-    SAPCU_TRY(gemm(m, W.D3a, cb, 64, 64, m->p(FD_R1_FC4_W), 64, m->p(FD_R1_FC4_B), W.D3c, 64, EPI_RESID_GELU, st, nullptr, 0, W.D3b, 64));
-    SAPCU_TRY(gemm(m, W.D3c, cb, 64, 64, m->p(FD_QKV_W), 192, m->p(FD_QKV_B), W.QKV, 192, EPI_BIAS, st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.ENC, cb, emb, emb, m->p(FD_FCIN_W), 256, m->p(FD_FCIN_B), W.D1, 256, EPI_GELU), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D1, cb, 256, 256, m->p(FD_R0_FC0_W), 128, m->p(FD_R0_FC0_B), W.D2a, 128, EPI_GELU), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D1, cb, 256, 256, m->p(FD_R0_PROJ_W), 128, m->p(FD_R0_PROJ_B), W.D2b, 128, EPI_BIAS), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D2a, cb, 128, 128, m->p(FD_R0_FC4_W), 128, m->p(FD_R0_FC4_B), W.D2c, 128, EPI_RESID_GELU).residual(W.D2b, 128),
+                       st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D2c, cb, 128, 128, m->p(FD_R1_FC0_W), 64, m->p(FD_R1_FC0_B), W.D3a, 64, EPI_GELU), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D2c, cb, 128, 128, m->p(FD_R1_PROJ_W), 64, m->p(FD_R1_PROJ_B), W.D3b, 64, EPI_BIAS), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D3a, cb, 64, 64, m->p(FD_R1_FC4_W), 64, m->p(FD_R1_FC4_B), W.D3c, 64, EPI_RESID_GELU).residual(W.D3b, 64), st));
+    SAPCU_TRY(run_gemm(m, Gemm(W.D3c, cb, 64, 64, m->p(FD_QKV_W), 192, m->p(FD_QKV_B), W.QKV, 192, EPI_BIAS), st));
     return launch_fd_tail(W.D3c, W.QKV, cb, m->heads, m->p(FD_WO_T), m->p(FD_BO), m->p(FD_LN_W), m->p(FD_LN_B), m->p(FD_WH_T),
                           m->p(FD_BH), m->p(FD_WD), m->p(FD_BD), W.ATT, dist + s, st);
 }
@@ -793,10 +826,7 @@ static int fd_forward(const sapcu_model* m, const float* patch, int64_t b, int m
                       float* dist, void* ws, int64_t ws_bytes, void* const* taps, hipStream_t st) {
     const FdPlan pl = fd_plan(m, b, mp);
     const FdWs W = fd_ws_layout(ws_align256(ws), m, pl, mp);
-    if (ws_bytes < (int64_t)W.bytes + 256) {
-        set_error("fd_forward: workspace %lld B < required %lld B", (long long)ws_bytes, (long long)W.bytes + 256);
-        return SAPCU_ERR_WORKSPACE;
-    }
+    SAPCU_TRY(check_workspace("fd_forward", ws_bytes, W.bytes));
     for (int64_t s = 0; s < b; s += pl.cb) {
         const FdChunk c{patch + s * mp * 3, s, (b - s) < pl.cb ? (b - s) : pl.cb, b, mp, knn_force, taps};
         if (pl.fused) {
@@ -904,17 +934,6 @@ int sapcu_l2_normalize3(const float* in, float* out, int64_t b, void* stream) {
     return launch_l2_normalize3(in, out, b, (hipStream_t)stream);
 }
 
-static int split_into_ws(const float* w, int64_t cnt, void* w16_ws, GemmArgs& g, hipStream_t st) {
-    char* base = (char*)w16_ws;            // hi (2*cnt B) | lo (2*cnt B) | overflow counter
-    int* ovf = (int*)(base + 4 * cnt);
-    SAPCU_CHECK_HIP(hipMemsetAsync(ovf, 0, sizeof(int), st));
-    SAPCU_TRY(launch_split_weights(w, cnt, base, base + 2 * cnt, ovf, st));
-    g.w16_hi = (const _Float16*)base;
-    g.w16_lo = (const _Float16*)(base + 2 * cnt);
-    g.ovf = ovf;
-    return SAPCU_OK;
-}
-
 int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, int n, const float* bias,
                    const float* lif4, int lif_steps, float* c, int ldc, void* w16_ws, int a_split_rows, int c_split_rows,
                    void* stream) {
@@ -925,20 +944,12 @@ int sapcu_gemm_f32(const float* a, int64_t r, int k, int lda, const float* w, in
     SAPCU_CHECK_ARG(r == 0 || (k > 0 && k % 32 == 0 && lda >= k && ldc >= n), "gemm: need k %% 32 == 0, lda >= k and ldc >= n (k=%d lda=%d n=%d ldc=%d)", k, lda, n, ldc);
     SAPCU_CHECK_ARG(r == 0 || ((((uintptr_t)a | (uintptr_t)w | (uintptr_t)w16_ws) & 15) == 0 && lda % (a_split_rows ? 8 : 4) == 0),
                     "gemm: A, W and w16_ws must be 16-byte aligned, lda %% 4 == 0 (%% 8 for split rows) (lda=%d)", lda);
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = a; g.r = r; g.k = k; g.lda = lda; g.w = w; g.n = n; g.bias = bias; g.c = c; g.ldc = ldc;
-    g.epi = lif4 ? EPI_LIF : EPI_BIAS; g.lif = lif4; g.lif_T = lif_steps;
-    g.a_split = a_split_rows ? 1 : 0; g.c_split = c_split_rows ? 1 : 0;
-    if (w16_ws && (g.a_split || k % 64 == 0)) {   // f32-A split-f16 kernel steps k by 64; other depths run on exact f32
-        SAPCU_TRY(split_into_ws(w, (int64_t)n * k, w16_ws, g, (hipStream_t)stream));
-        // a_split_rows = 2: the ring kernel even where the big-tile kernel takes the shape (bit-identical; parity tests)
-        if (g.a_split) return launch_gemm_split_rows(g, (hipStream_t)stream, a_split_rows != 2);
-        if (!env_is("SAPCU_SHORTK", "0") && gemm_shortk_ok(g)) return launch_gemm_shortk(g, (hipStream_t)stream);
-        return launch_gemm_sf16(g, (hipStream_t)stream);
-    }
-    SAPCU_CHECK_ARG(!g.c_split, "gemm: split-row output needs k %% 64 == 0 on the f32-A path");
-    return launch_gemm(g, (hipStream_t)stream);
+    Gemm g(a, r, k, lda, w, n, bias, c, ldc, lif4 ? EPI_LIF : EPI_BIAS);
+    g.neuron(lif4, lif_steps).split_in(a_split_rows != 0).split_out(c_split_rows != 0);
+    // a_split_rows = 2: the ring kernel even where the big-tile kernel takes the shape (bit-identical; parity tests)
+    const SplitWs sw(w16_ws, (int64_t)n * k);
+    if (w16_ws) sw.attach(g);
+    return gemm_run(g, w16_ws != nullptr, a_split_rows != 2, !env_is("SAPCU_SHORTK", "0"), (hipStream_t)stream, &sw);
 }
 
 int sapcu_to_split_rows(const float* in, int64_t rows, int k, int ld_in, float* out, int ld_out, void* stream) {
@@ -957,22 +968,15 @@ int sapcu_posenc_gemm_f32(const float* pe1, int64_t r, int d, const float* w, co
     SAPCU_CHECK_ARG(d % 32 == 0, "posenc_gemm: d=%d must be a multiple of 32", d);
     SAPCU_CHECK_ARG((((uintptr_t)pe1 | (uintptr_t)w | (uintptr_t)w16_ws) & 15) == 0 && ((uintptr_t)edge_table_ws & 7) == 0,
                     "posenc_gemm: pe1, w and w16_ws must be 16-byte aligned, edge_table_ws 8-byte aligned");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a = pe1; g.r = r; g.k = d; g.lda = d; g.w = w; g.n = d; g.bias = bias; g.c = pe_out; g.ldc = d;
-    g.epi = EPI_LIF_ATTN; g.lif = lif4; g.lif_T = lif_steps; g.c2 = attn_in_out;
-    g.q = qkv; g.kf = qkv + d; g.ldq = 3 * d; g.tab = (const int2*)edge_table_ws;
+    // split_rows: the production form, pe1 arrives as split rows and attn_in leaves as split rows; 2: ring kernel only
+    Gemm g(pe1, r, d, d, w, d, bias, pe_out, d, EPI_LIF_ATTN);
+    g.neuron(lif4, lif_steps).attn(attn_in_out, qkv, d, (const int2*)edge_table_ws).split_in(split_rows != 0).split_out2(split_rows != 0);
+    const SplitWs sw(w16_ws, (int64_t)d * d);
+    if (w16_ws) sw.attach(g);
+    const char* why = nullptr;      // the route asked once more up here: its refusals, too, come before the edge table is written
+    SAPCU_CHECK_ARG(gemm_route(g, w16_ws != nullptr, split_rows != 2, false, &why), "%s", why);
     SAPCU_TRY(launch_edge_table(idx, r, m_pts, kk, (int2*)edge_table_ws, (hipStream_t)stream));
-    if (w16_ws && (split_rows || d % 64 == 0)) {   // split W into the caller's scratch (hi | lo | counter), then 3 x f16 MFMA
-        SAPCU_TRY(split_into_ws(w, (int64_t)d * d, w16_ws, g, (hipStream_t)stream));
-        if (split_rows) {     // the production form: pe1 arrives as split rows, attn_in leaves as split rows
-            g.a_split = 1;
-            g.c2_split = 1;
-            return launch_gemm_split_rows(g, (hipStream_t)stream, split_rows != 2);     // split_rows = 2: ring kernel only
-        }
-        return launch_gemm_sf16(g, (hipStream_t)stream);
-    }
-    return launch_gemm(g, (hipStream_t)stream);
+    return gemm_run(g, w16_ws != nullptr, split_rows != 2, false, (hipStream_t)stream, &sw);
 }
 
 // workspace of sapcu_fn_edge_chain_f32 (base: the caller's pointer aligned up, or null for the size; the sizer adds 256 bytes)
@@ -1014,22 +1018,16 @@ int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t poin
                         res_out && workspace, "fn_edge_chain: null pointer");
     SAPCU_CHECK_ARG(fn_edge_chain_ok(d, kk), "fn_edge_chain: unsupported shape (d=%d kk=%d)", d, kk);
     SAPCU_CHECK_ARG(points >= 0 && m_pts >= kk && heads >= 1 && d % heads == 0 && lif_steps >= 1, "fn_edge_chain: bad sizes");
-    const int64_t need = sapcu_fn_edge_chain_workspace_bytes(points, d, kk);
-    if (workspace_bytes < need) {
-        set_error("fn_edge_chain: workspace %lld B < required %lld B", (long long)workspace_bytes, (long long)need);
-        return SAPCU_ERR_WORKSPACE;
-    }
     hipStream_t st = (hipStream_t)stream;
     const ChainWs W = chain_ws_layout(ws_align256(workspace), points, d, kk);
+    SAPCU_TRY(check_workspace("fn_edge_chain", workspace_bytes, W.bytes));
     const float* ws[3] = {w1, w2, w3};
     for (int q = 0; q < 3; ++q) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        SAPCU_TRY(split_into_ws(ws[q], (int64_t)d * d, W.split[q], g, st));
-        SAPCU_TRY(launch_pack_chain_weights(g.w16_hi, g.w16_lo, d, W.packed[q], st));
+        const SplitWs sw(W.split[q], (int64_t)d * d);
+        SAPCU_TRY(sw.fill(ws[q], st));
+        SAPCU_TRY(launch_pack_chain_weights(sw.hi, sw.lo, d, W.packed[q], st));
     }
-    ChainArgs ca;
-    memset(&ca, 0, sizeof(ca));
+    ChainArgs ca{};
     ca.P = points; ca.m = m_pts; ca.qkv = qkv; ca.ldq = 3 * d;
     ca.wd = w_delta; ca.bd = b_delta; ca.lifd = lif_delta;
     ca.w1p = W.packed[0]; ca.b1 = b1; ca.lif1 = lif1;
@@ -1043,7 +1041,7 @@ int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t poin
     // (16 slots of 8 bytes per group, at most points / 4 + 1 groups), and SAPCU_CHAIN_TRIM=0 is honoured at every call
     {
         const int64_t sbytes = (points / 4 + 1) * 16 * 8;
-        const int64_t off = (need + 255) / 256 * 256;
+        const int64_t off = ((int64_t)W.bytes + 256 + 255) / 256 * 256;
         if (workspace_bytes >= off + sbytes + 256) ca.stamps = (unsigned long long*)((char*)ws_align256(workspace) + off);
         if (env_is("SAPCU_CHAIN_TRIM", "0")) ca.trim = 0;
     }
@@ -1051,169 +1049,151 @@ int sapcu_fn_edge_chain_f32(const float* patch, const int32_t* idx, int64_t poin
     return launch_fn_edge_chain(ca, patch, idx, d, kk, W.tab, W.pd, st);
 }
 
+// ---- sapcu_model_create, stage by stage: each returns a status; the handle under construction frees itself on any failure
+static int parse_fn_hparams(sapcu_model* m, const int32_t* hp, int n_hp, int n_dir) {
+    SAPCU_CHECK_ARG(n_hp == 6 && n_dir == FN_SLOTS, "model_create(fn): need 6 hparams and %d slots (got %d, %d)", (int)FN_SLOTS, n_hp, n_dir);
+    m->kv[0] = hp[0]; m->kv[1] = hp[1]; m->kv[2] = hp[2];
+    m->emb = hp[3]; m->T = hp[4]; m->heads = hp[5];
+    SAPCU_CHECK_ARG(m->kv[0] >= 1 && m->kv[1] >= 1 && m->kv[2] >= 1 && m->emb >= 32 && m->emb % 32 == 0 && m->T >= 1 && m->heads >= 1 &&
+                        128 % m->heads == 0,
+                    "model_create(fn): unsupported hyper-parameters");
+    return SAPCU_OK;
+}
+
+static int parse_fd_hparams(sapcu_model* m, const int32_t* hp, int n_hp, int n_dir) {
+    SAPCU_CHECK_ARG(n_hp >= 6 && n_dir == FD_SLOTS && hp[4] >= 1 && hp[4] <= 8 && n_hp == 5 + hp[4],
+                    "model_create(fd): need [k,emb,T,heads,S,ks...] and %d slots", (int)FD_SLOTS);
+    m->k = hp[0]; m->emb = hp[1]; m->T = hp[2]; m->heads = hp[3]; m->nscale = hp[4];
+    for (int i = 0; i < m->nscale; ++i) m->ks[i] = hp[5 + i];
+    SAPCU_CHECK_ARG(m->k >= 1 && m->emb >= 32 && m->emb % 32 == 0 && m->T >= 1 && m->T <= 64, "model_create(fd): unsupported hyper-parameters");
+    // the decoder's attention splits 64 channels into heads on the lanes of one wave (launch_fd_tail checks it again)
+    SAPCU_CHECK_ARG(m->heads >= 1 && m->heads <= 64 && (m->heads & (m->heads - 1)) == 0,
+                    "model_create(fd): num_heads must be a power of two <= 64 (got %d)", m->heads);
+    for (int i = 0; i < m->nscale; ++i) SAPCU_CHECK_ARG(m->ks[i] >= 1, "model_create(fd): k_scales[%d] = %d, need >= 1", i, m->ks[i]);
+    return SAPCU_OK;
+}
+
+static int check_slot_directory(sapcu_model* m, const int64_t* dir_host, int n_dir, int64_t blob_floats) {
+    m->dir.assign(dir_host, dir_host + n_dir);
+    for (int i = 0; i < n_dir; ++i)
+        SAPCU_CHECK_ARG(m->dir[i] >= 0 && m->dir[i] < blob_floats && (m->dir[i] & 3) == 0,
+                        "model_create: slot %d offset %lld out of range / unaligned", i, (long long)m->dir[i]);
+    return SAPCU_OK;
+}
+
+// the caller's blob on the device and, for fn with the fold on, W' [64, d] | b' [64] of the three blocks behind it (256-byte aligned pieces)
+static int copy_blob_and_fold(sapcu_model* m, const float* blob, int64_t blob_floats) {
+    int64_t total = blob_floats;
+    if (m->kind == SAPCU_KIND_FN && m->opt_fn_fold_out) {
+        total = (total + 63) & ~(int64_t)63;
+        for (int l = 0; l < 3; ++l) {
+            m->fold_w[l] = total;
+            total += (int64_t)64 * (128 << l);
+            m->fold_b[l] = total;
+            total += 64;
+        }
+    }
+    m->blob_floats = total;
+    SAPCU_CHECK_HIP(hipMalloc((void**)&m->blob, (size_t)total * 4));
+    SAPCU_CHECK_HIP(hipMemcpy(m->blob, blob, (size_t)blob_floats * 4, hipMemcpyDeviceToDevice));
+    if (total == blob_floats) return SAPCU_OK;
+    SAPCU_CHECK_HIP(hipMemset(m->blob + blob_floats, 0, (size_t)(total - blob_floats) * 4));
+    for (int l = 0; l < 3; ++l) {
+        // W' = W_fc2 . W_out, b' = W_fc2 . b_out + b_fc2 on the host in f64 (once per model), before the weights are split
+        const int d = 128 << l, sb = FN_BLK0 + l * B_SLOTS;
+        const int64_t need[4] = {(int64_t)d * d, d, (int64_t)64 * d, 64};
+        static const int slot[4] = {B_OUT_W, B_OUT_B, B_FC2_W, B_FC2_B};
+        std::vector<float> h[4], wf((size_t)64 * d), bf(64);
+        for (int q = 0; q < 4; ++q) {
+            SAPCU_CHECK_ARG(m->dir[sb + slot[q]] + need[q] <= blob_floats, "model_create(fn): slot %d runs past the end of the blob", sb + slot[q]);
+            h[q].resize((size_t)need[q]);
+            SAPCU_CHECK_HIP(hipMemcpy(h[q].data(), m->p(sb + slot[q]), (size_t)need[q] * 4, hipMemcpyDeviceToHost));
+        }
+        fold_affine_f64(h[0].data(), h[1].data(), h[2].data(), h[3].data(), d, 64, wf.data(), bf.data());
+        SAPCU_CHECK_HIP(hipMemcpy(m->blob + m->fold_w[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
+        SAPCU_CHECK_HIP(hipMemcpy(m->blob + m->fold_b[l], bf.data(), bf.size() * 4, hipMemcpyHostToDevice));
+    }
+    return SAPCU_OK;
+}
+
+// the overflow counters; in split-f16 mode the whole blob as f16 hi / lo planes — a parameter beyond the f16 range: exact-f32 kernels
+static int split_blob_f16(sapcu_model* m) {
+    SAPCU_CHECK_HIP(hipMalloc((void**)&m->ovf_dev, 2 * sizeof(int)));
+    SAPCU_CHECK_HIP(hipMemset(m->ovf_dev, 0, 2 * sizeof(int)));
+    if (!m->sf16) return SAPCU_OK;
+    SAPCU_CHECK_HIP(hipMalloc(&m->w16_hi, (size_t)m->blob_floats * 2));
+    SAPCU_CHECK_HIP(hipMalloc(&m->w16_lo, (size_t)m->blob_floats * 2));
+    int wovf = 0;
+    SAPCU_TRY(launch_split_weights(m->blob, m->blob_floats, m->w16_hi, m->w16_lo, m->ovf_dev + 1, nullptr));
+    SAPCU_CHECK_HIP(hipMemcpy(&wovf, m->ovf_dev + 1, sizeof(int), hipMemcpyDeviceToHost));
+    if (wovf != 0) m->sf16 = false;
+    return SAPCU_OK;
+}
+
+// fn blocks 1-3 (d = 128, 256, 512): the three d x d matrices of the edge chain again in MFMA-fragment order
+static int pack_fn_chain_weights(sapcu_model* m) {
+    if (!m->sf16 || m->kind != SAPCU_KIND_FN) return SAPCU_OK;
+    SAPCU_CHECK_HIP(hipMalloc(&m->chain_w, (size_t)chain_w_off(3, 0) * 2));
+    for (int l = 0; l < 3; ++l) {
+        static const int slots[3] = {B_DELTA2_W, B_GAMMA_W, B_GAMMA2_W};
+        for (int q = 0; q < 3; ++q) {
+            const int64_t wo = m->dir[FN_BLK0 + l * B_SLOTS + slots[q]];
+            SAPCU_TRY(launch_pack_chain_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, 128 << l,
+                                                (_Float16*)m->chain_w + chain_w_off(l, q), nullptr));
+        }
+    }
+    SAPCU_CHECK_HIP(hipDeviceSynchronize());
+    return SAPCU_OK;
+}
+
+// fd: the scale table and the gate counter; the fused encoder's operands — five matrices in fragment order (hi | lo planes interleaved
+// per fragment), neuron parameters clamped once.  More than four scales: the fused encoder does not take the model, fd_msc_kernel (the
+// x0 path) does — it reads multi_scale_conv and the neuron parameters only, so the first four matrices stay out (first = 4)
+static int pack_fd_encoder(sapcu_model* m) {
+    if (m->kind != SAPCU_KIND_FD) return SAPCU_OK;
+    SAPCU_CHECK_HIP(hipMalloc((void**)&m->ks_dev, 8 * sizeof(int32_t)));
+    SAPCU_CHECK_HIP(hipMemcpy(m->ks_dev, m->ks, 8 * sizeof(int32_t), hipMemcpyHostToDevice));
+    SAPCU_CHECK_HIP(hipMalloc((void**)&m->gate_dev, sizeof(int)));
+    SAPCU_CHECK_HIP(hipMemset(m->gate_dev, 0, sizeof(int)));
+    if (!m->sf16 || m->emb < 96) return SAPCU_OK;
+    const int first = m->nscale <= 4 ? 0 : 4;
+    const int mats[5][3] = {{FD_FUSE_W, 64, 64 * m->nscale}, {FD_EDGE1_W, 256, 64}, {FD_EDGE2_W, 512, 128},
+                            {FD_EDGE3_W, 1024, 256}, {FD_MSC_W, m->emb, 960}};
+    int64_t halves = 0;
+    for (int i = 0; i < 5; ++i) {
+        m->fde_off[i] = halves;
+        if (i >= first) halves += (int64_t)2 * mats[i][1] * mats[i][2];
+    }
+    SAPCU_CHECK_HIP(hipMalloc(&m->fde_w, (size_t)halves * 2));
+    SAPCU_CHECK_HIP(hipMalloc((void**)&m->fde_nprm, 960 * 8 * sizeof(float)));
+    for (int i = first; i < 5; ++i) {
+        const int64_t wo = m->dir[mats[i][0]];
+        SAPCU_TRY(launch_pack_frag_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, mats[i][1], mats[i][2],
+                                           (_Float16*)m->fde_w + m->fde_off[i], nullptr));
+    }
+    static const int nslot[4] = {FD_SNN0, FD_SNN1, FD_SNN2, FD_SNN3};
+    for (int i = 0; i < 4; ++i) SAPCU_TRY(launch_pack_fd_neuron(m->p(nslot[i]), FD_COUT[i], i < 2 ? 1 : 0, FD_COFF[i], m->fde_nprm, nullptr));
+    SAPCU_CHECK_HIP(hipDeviceSynchronize());
+    return SAPCU_OK;
+}
+
 int sapcu_model_create(int kind, const int32_t* hp, int n_hp, const float* blob, int64_t blob_floats,
                        const int64_t* dir_host, int n_dir, sapcu_model_t* out) {
     SAPCU_CHECK_ARG(hp && blob && dir_host && out && blob_floats > 0, "model_create: null pointer");
-    sapcu_model* m = new (std::nothrow) sapcu_model();
+    // owns the handle until it is handed out: a failing stage frees whatever the stages before it allocated (free_model)
+    std::unique_ptr<sapcu_model, void (*)(sapcu_model*)> owner(new (std::nothrow) sapcu_model(), free_model);
+    sapcu_model* const m = owner.get();
     SAPCU_CHECK_ARG(m != nullptr, "model_create: out of host memory");
     m->kind = kind;
     read_env_switches(m);
-    int rc = SAPCU_OK;
-    if (kind == SAPCU_KIND_FN) {
-        if (n_hp != 6 || n_dir != FN_SLOTS) {
-            set_error("model_create(fn): need 6 hparams and %d slots (got %d, %d)", (int)FN_SLOTS, n_hp, n_dir);
-            rc = SAPCU_ERR_ARG;
-        } else {
-            m->kv[0] = hp[0]; m->kv[1] = hp[1]; m->kv[2] = hp[2];
-            m->emb = hp[3]; m->T = hp[4]; m->heads = hp[5];
-            if (m->kv[0] < 1 || m->kv[1] < 1 || m->kv[2] < 1 || m->emb < 32 || m->emb % 32 || m->T < 1 || m->heads < 1 ||
-                128 % m->heads) {
-                set_error("model_create(fn): unsupported hyper-parameters");
-                rc = SAPCU_ERR_ARG;
-            }
-        }
-    } else if (kind == SAPCU_KIND_FD) {
-        if (n_hp < 6 || n_dir != FD_SLOTS || hp[4] < 1 || hp[4] > 8 || n_hp != 5 + hp[4]) {
-            set_error("model_create(fd): need [k,emb,T,heads,S,ks...] and %d slots", (int)FD_SLOTS);
-            rc = SAPCU_ERR_ARG;
-        } else {
-            m->k = hp[0]; m->emb = hp[1]; m->T = hp[2]; m->heads = hp[3]; m->nscale = hp[4];
-            for (int i = 0; i < m->nscale; ++i) m->ks[i] = hp[5 + i];
-            if (m->k < 1 || m->emb < 32 || m->emb % 32 || m->T < 1 || m->T > 64) {
-                set_error("model_create(fd): unsupported hyper-parameters");
-                rc = SAPCU_ERR_ARG;
-            } else if (m->heads < 1 || m->heads > 64 || (m->heads & (m->heads - 1))) {
-                // the decoder's attention splits 64 channels into heads on the lanes of one wave (launch_fd_tail checks it again)
-                set_error("model_create(fd): num_heads must be a power of two <= 64 (got %d)", m->heads);
-                rc = SAPCU_ERR_ARG;
-            }
-            for (int i = 0; i < m->nscale && rc == SAPCU_OK; ++i)
-                if (m->ks[i] < 1) {
-                    set_error("model_create(fd): k_scales[%d] = %d, need >= 1", i, m->ks[i]);
-                    rc = SAPCU_ERR_ARG;
-                }
-        }
-    } else {
-        set_error("model_create: unknown kind %d", kind);
-        rc = SAPCU_ERR_ARG;
-    }
-    if (rc == SAPCU_OK) {
-        m->dir.assign(dir_host, dir_host + n_dir);
-        for (int i = 0; i < n_dir; ++i)
-            if (m->dir[i] < 0 || m->dir[i] >= blob_floats || (m->dir[i] & 3)) {
-                set_error("model_create: slot %d offset %lld out of range / unaligned", i, (long long)m->dir[i]);
-                rc = SAPCU_ERR_ARG;
-                break;
-            }
-    }
-    auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == SAPCU_OK) {
-            set_error("model_create: %s failed: %s", what, hipGetErrorString(e));
-            rc = SAPCU_ERR_HIP;
-        }
-    };
-    if (rc == SAPCU_OK) {
-        // fn with the fold on: room behind the caller's blob for W' [64, d] | b' [64] of the three blocks (256-byte aligned pieces)
-        int64_t total = blob_floats;
-        if (kind == SAPCU_KIND_FN && m->opt_fn_fold_out) {
-            total = (total + 63) & ~(int64_t)63;
-            for (int l = 0; l < 3; ++l) {
-                m->fold_w[l] = total;
-                total += (int64_t)64 * (128 << l);
-                m->fold_b[l] = total;
-                total += 64;
-            }
-        }
-        m->blob_floats = total;
-        hip_ok(hipMalloc((void**)&m->blob, (size_t)total * 4), "hipMalloc(blob)");
-        if (rc == SAPCU_OK) hip_ok(hipMemcpy(m->blob, blob, (size_t)blob_floats * 4, hipMemcpyDeviceToDevice), "copy blob");
-        if (rc == SAPCU_OK && total > blob_floats)
-            hip_ok(hipMemset(m->blob + blob_floats, 0, (size_t)(total - blob_floats) * 4), "memset folded parameters");
-        for (int l = 0; l < 3 && rc == SAPCU_OK && total > blob_floats; ++l) {
-            // W' = W_fc2 . W_out, b' = W_fc2 . b_out + b_fc2 on the host in f64 (once per model), before the split below
-            const int d = 128 << l, sb = FN_BLK0 + l * B_SLOTS;
-            const int64_t need[4] = {(int64_t)d * d, d, (int64_t)64 * d, 64};
-            static const int slot[4] = {B_OUT_W, B_OUT_B, B_FC2_W, B_FC2_B};
-            std::vector<float> h[4], wf((size_t)64 * d), bf(64);
-            for (int q = 0; q < 4 && rc == SAPCU_OK; ++q) {
-                if (m->dir[sb + slot[q]] + need[q] > blob_floats) {
-                    set_error("model_create(fn): slot %d runs past the end of the blob", sb + slot[q]);
-                    rc = SAPCU_ERR_ARG;
-                    break;
-                }
-                h[q].resize((size_t)need[q]);
-                hip_ok(hipMemcpy(h[q].data(), m->p(sb + slot[q]), (size_t)need[q] * 4, hipMemcpyDeviceToHost), "read out_proj / fc2");
-            }
-            if (rc != SAPCU_OK) break;
-            fold_affine_f64(h[0].data(), h[1].data(), h[2].data(), h[3].data(), d, 64, wf.data(), bf.data());
-            hip_ok(hipMemcpy(m->blob + m->fold_w[l], wf.data(), wf.size() * 4, hipMemcpyHostToDevice), "copy folded weights");
-            if (rc == SAPCU_OK) hip_ok(hipMemcpy(m->blob + m->fold_b[l], bf.data(), bf.size() * 4, hipMemcpyHostToDevice), "copy folded bias");
-        }
-        if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->ovf_dev, 2 * sizeof(int)), "hipMalloc(ovf)");
-        if (rc == SAPCU_OK) hip_ok(hipMemset(m->ovf_dev, 0, 2 * sizeof(int)), "memset ovf");
-        if (rc == SAPCU_OK && m->sf16) {
-            hip_ok(hipMalloc(&m->w16_hi, (size_t)total * 2), "hipMalloc(w16_hi)");
-            if (rc == SAPCU_OK) hip_ok(hipMalloc(&m->w16_lo, (size_t)total * 2), "hipMalloc(w16_lo)");
-            if (rc == SAPCU_OK) {
-                int wovf = 0;
-                if (launch_split_weights(m->blob, total, m->w16_hi, m->w16_lo, m->ovf_dev + 1, nullptr) != SAPCU_OK)
-                    rc = SAPCU_ERR_HIP;
-                if (rc == SAPCU_OK) hip_ok(hipMemcpy(&wovf, m->ovf_dev + 1, sizeof(int), hipMemcpyDeviceToHost), "read ovf");
-                if (rc == SAPCU_OK && wovf != 0) m->sf16 = false;   // a parameter exceeds the f16 range: exact-f32 kernels
-            }
-            // fn blocks 1-3 (d = 128, 256, 512): the three d x d matrices of the edge chain again in MFMA-fragment order
-            if (rc == SAPCU_OK && m->sf16 && kind == SAPCU_KIND_FN) {
-                hip_ok(hipMalloc(&m->chain_w, (size_t)chain_w_off(3, 0) * 2), "hipMalloc(chain_w)");
-                for (int l = 0; l < 3 && rc == SAPCU_OK; ++l) {
-                    const int d = 128 << l;
-                    static const int slots[3] = {B_DELTA2_W, B_GAMMA_W, B_GAMMA2_W};
-                    for (int q = 0; q < 3 && rc == SAPCU_OK; ++q) {
-                        const int64_t wo = m->dir[FN_BLK0 + l * B_SLOTS + slots[q]];
-                        if (launch_pack_chain_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, d,
-                                                      (_Float16*)m->chain_w + chain_w_off(l, q), nullptr) != SAPCU_OK)
-                            rc = SAPCU_ERR_HIP;
-                    }
-                }
-                if (rc == SAPCU_OK) hip_ok(hipDeviceSynchronize(), "pack chain weights");
-            }
-        }
-        if (rc == SAPCU_OK && kind == SAPCU_KIND_FD) {
-            hip_ok(hipMalloc((void**)&m->ks_dev, 8 * sizeof(int32_t)), "hipMalloc(ks)");
-            if (rc == SAPCU_OK) hip_ok(hipMemcpy(m->ks_dev, m->ks, 8 * sizeof(int32_t), hipMemcpyHostToDevice), "copy ks");
-            if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->gate_dev, sizeof(int)), "hipMalloc(gate)");
-            if (rc == SAPCU_OK) hip_ok(hipMemset(m->gate_dev, 0, sizeof(int)), "memset gate");
-            // the fused encoder's operands: five matrices in fragment order (hi | lo planes interleaved per fragment), neuron
-            // parameters clamped once.  More than four scales: the fused encoder does not take the model, fd_msc_kernel (the x0 path)
-            // does — it reads multi_scale_conv and the neuron parameters only, so the first four matrices stay out (first = 4)
-            if (rc == SAPCU_OK && m->sf16 && m->emb >= 96) {
-                const int first = m->nscale <= 4 ? 0 : 4;
-                const int mats[5][3] = {{FD_FUSE_W, 64, 64 * m->nscale}, {FD_EDGE1_W, 256, 64}, {FD_EDGE2_W, 512, 128},
-                                        {FD_EDGE3_W, 1024, 256}, {FD_MSC_W, m->emb, 960}};
-                int64_t halves = 0;
-                for (int i = 0; i < 5; ++i) {
-                    m->fde_off[i] = halves;
-                    if (i >= first) halves += (int64_t)2 * mats[i][1] * mats[i][2];
-                }
-                hip_ok(hipMalloc(&m->fde_w, (size_t)halves * 2), "hipMalloc(fde_w)");
-                if (rc == SAPCU_OK) hip_ok(hipMalloc((void**)&m->fde_nprm, 960 * 8 * sizeof(float)), "hipMalloc(fde_nprm)");
-                for (int i = first; i < 5 && rc == SAPCU_OK; ++i) {
-                    const int64_t wo = m->dir[mats[i][0]];
-                    if (launch_pack_frag_weights((const _Float16*)m->w16_hi + wo, (const _Float16*)m->w16_lo + wo, mats[i][1], mats[i][2],
-                                                 (_Float16*)m->fde_w + m->fde_off[i], nullptr) != SAPCU_OK)
-                        rc = SAPCU_ERR_HIP;
-                }
-                static const int nslot[4] = {FD_SNN0, FD_SNN1, FD_SNN2, FD_SNN3}, nch[4] = {64, 128, 256, 512}, noff[4] = {0, 64, 192, 448};
-                for (int i = 0; i < 4 && rc == SAPCU_OK; ++i)
-                    if (launch_pack_fd_neuron(m->p(nslot[i]), nch[i], i < 2 ? 1 : 0, noff[i], m->fde_nprm, nullptr) != SAPCU_OK) rc = SAPCU_ERR_HIP;
-                if (rc == SAPCU_OK) hip_ok(hipDeviceSynchronize(), "pack fd encoder operands");
-            }
-        }
-    }
-    if (rc != SAPCU_OK) {
-        free_model(m);
-        return rc;
-    }
-    *out = m;
+    SAPCU_CHECK_ARG(kind == SAPCU_KIND_FN || kind == SAPCU_KIND_FD, "model_create: unknown kind %d", kind);
+    SAPCU_TRY(kind == SAPCU_KIND_FN ? parse_fn_hparams(m, hp, n_hp, n_dir) : parse_fd_hparams(m, hp, n_hp, n_dir));
+    SAPCU_TRY(check_slot_directory(m, dir_host, n_dir, blob_floats));
+    SAPCU_TRY(copy_blob_and_fold(m, blob, blob_floats));
+    SAPCU_TRY(split_blob_f16(m));
+    SAPCU_TRY(pack_fn_chain_weights(m));
+    SAPCU_TRY(pack_fd_encoder(m));
+    *out = owner.release();
     return SAPCU_OK;
 }
 
