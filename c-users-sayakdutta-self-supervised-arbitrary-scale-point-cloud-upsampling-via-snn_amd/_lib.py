@@ -239,6 +239,15 @@ POISSON_SIGNATURES = {
                                             c_int64, c_void_p]),
 }
 POISSON_EXPORTS = tuple(POISSON_SIGNATURES)
+# csrc/sapcu_pointing.h: fn's seed-centred samples, the band of candidates off a surface cloud with their pointing directions
+# (sapcu_amd/pointing.py); info_host is a HOST int64[4], every other pointer a DEVICE array.  Beside TABLES for the same reason
+POINTING_SIGNATURES = {
+    "sapcu_pointing_workspace_bytes": (c_int64, [c_int64, c_int64, c_int, c_int]),
+    "sapcu_pointing_samples_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_double, c_double,
+                                           c_void_p, c_int, c_double, c_double, c_double, c_int64] + [c_void_p] * 7 +
+                                   [c_void_p, c_int64, POINTER(c_int64), c_void_p]),
+}
+POINTING_EXPORTS = tuple(POINTING_SIGNATURES)
 _lib = None
 
 
@@ -256,7 +265,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
     except OSError as e:  # missing ROCm runtime etc.
         raise SapcuLibraryError("cannot load %s: %s" % (p, e)) from e
-    for name, (res, args) in ((name, sig) for table in list(TABLES.values()) + [GEODESIC_SIGNATURES, POISSON_SIGNATURES] for name, sig in table.items()):
+    for name, (res, args) in ((name, sig) for table in list(TABLES.values()) + [GEODESIC_SIGNATURES, POISSON_SIGNATURES, POINTING_SIGNATURES] for name, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

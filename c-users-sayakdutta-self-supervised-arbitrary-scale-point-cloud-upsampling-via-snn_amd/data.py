@@ -13,6 +13,9 @@ from a device ``torch.Generator`` seeded by (seed, epoch, batch): deterministic,
 ``FdRayPatches`` yields fd's ray samples of one mesh per item (the reference's ``scripts/sample_mesh-rd.py`` -> ``fd.npz``), sampled
 and cast afresh on the device (``ray.sample_fd_rays``).  ``PoissonPU1KPatches`` yields ``PU1KPatches``'s batches from
 meshes: both clouds of a sample are Poisson-disk sampled afresh on the device (``poisson.poisson_disk_sample``).
+``FnPointingPatches`` and ``FdSeedPatches`` yield the batches of the reference's folder route (``fn/transform.py:Subsamplefn``,
+``fd/transform.py:Subsamplerfd``): patches centred on a seed OFF the surface, cut by the calls inference itself makes
+(``seed_patches``), from ``pointing.sample_fn_pointing`` and ``FdRayPatches.sample``.
 
 No CPU path: the HIP library and a device are required.
 """
@@ -23,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from . import _inputs, _lib, mesh as mesh_mod, poisson as poisson_mod, ray as ray_mod, surface
+from . import _inputs, _lib, generation, mesh as mesh_mod, pointing as pointing_mod, poisson as poisson_mod, ray as ray_mod, surface
 
 MAX_N, MAX_G, MAX_K = 4096, 65536, 128
 
@@ -431,9 +434,10 @@ class FdRayPatches(object):
         gen.manual_seed(((self.seed * 1000003 + self.epoch) * 1000003 + item + 1) & (2 ** 63 - 1))
         return gen
 
-    def sample(self, m, item=None):
-        """The item of mesh m of the split, from the generator of (seed, epoch, item); item None = m."""
-        gen = self._generator(int(m) if item is None else int(item))
+    def sample(self, m, item=None, gen=None):
+        """The item of mesh m of the split, from the generator of (seed, epoch, item); item None = m.  ``gen``: the draws come from
+        this device generator instead."""
+        gen = self._generator(int(m) if item is None else int(item)) if gen is None else gen
         n, dev = self.num_rays, self.device
         u = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64)
         r1 = torch.rand((n,), generator=gen, device=dev, dtype=torch.float64).float()
@@ -450,3 +454,140 @@ class FdRayPatches(object):
         order = torch.randperm(S, generator=self._generator(-1), device=self.device).tolist() if self.shuffle else list(range(S))
         for item, m in enumerate(order):
             yield self.sample(m, item)
+
+
+# ------------------------------------------------------------------------------------------------- seed-centred loaders
+def seed_patches(cloud_f32, queries, k, normals=None):
+    """Patches centred on seeds that need not lie on the cloud, cut by the calls ``Generator3D6._refine_pass`` makes at inference:
+    ``generation.knn_gather`` of ``queries`` f64 [P,3] in ``cloud_f32`` [n,3] widened to f64 -> f32 [P,k,3], the k nearest cloud
+    points minus the seed; with ``normals`` f32 [P,3] the rows go through ``generation.gather_rotate`` instead, which turns every
+    patch so that its normal lies on +x.  Device tensors; k > n: ValueError, as the reference's ``KDTree.query`` raises."""
+    dev_tensor = functools.partial(_inputs.device_tensor, getattr(cloud_f32, "device", None), "the cloud")
+    if not torch.is_tensor(cloud_f32):
+        raise ValueError("cloud: expected a device tensor")
+    if not cloud_f32.is_cuda:
+        raise RuntimeError("cloud: a CPU tensor (there is no CPU path)")
+    cloud = dev_tensor(cloud_f32, "cloud", torch.float32, (None, 3)).double()
+    q = dev_tensor(queries, "queries", torch.float64, (None, 3))
+    normals = dev_tensor(normals, "normals", torch.float32, (q.shape[0], 3), optional=True)
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k: need 1 <= k <= %d, got %d" % (MAX_K, k))
+    idx, _, patch = generation.knn_gather(cloud, q, k, want_patch=normals is None)
+    return patch if normals is None else generation.gather_rotate(cloud, q, idx, normals)
+
+
+def _seed_loader_checks(cloud_points, num_patches, k_neighbors):
+    if int(num_patches) < 1:
+        raise ValueError("num_patches must be >= 1")
+    if int(k_neighbors) > int(cloud_points):
+        raise ValueError("k_neighbors: %d neighbours of a cloud of %d points" % (int(k_neighbors), int(cloud_points)))
+
+
+class FnPointingPatches(_DeviceLoader):
+    """fn's batches of the reference's folder route, from the meshes themselves: ``fn/transform.py:Subsamplefn`` over what
+    ``scripts/sample_mesh-fn.py`` stores per mesh.  Per mesh of the split a surface cloud of ``surface_points`` points and up to
+    ``pointing_size`` pointing samples are made ONCE (``pointing.sample_fn_pointing``, on first use, from the generator of (seed,
+    mesh); ``resample()`` has them made anew, from other draws); ``geometry`` holds that call's lattice arguments.  A batch entry draws
+    ``cloud_points`` rows of the surface cloud and ``num_patches`` samples, both with replacement, and cuts the patches round the
+    samples' points (taken as f32, as ``fn/field.py:fnField`` loads them) with ``seed_patches``: ``input`` f32 [B,P,k,3], ``normal``
+    f32 [B,P,3] (the pointing directions), ``cloud`` f32 [B,cloud_points,3], ``index`` (the meshes' positions in the split).  The
+    draws come from the (seed, epoch, batch) generator, per entry the cloud's rows, then the samples; ``last_draws`` holds them
+    (``cloud_idx``, ``sample_idx``) with the ``queries`` f64 [B,P,3].  A mesh without a pointing sample: ValueError."""
+
+    def __init__(self, meshes, surface_points=100000, pointing_size=50000, cloud_points=1024, num_patches=8, k_neighbors=64, split="train",
+                 batch_size=4, shuffle=True, seed=0, device=None, drop_last=False, geometry=None):
+        _seed_loader_checks(cloud_points, num_patches, k_neighbors)
+        if int(surface_points) < 1 or int(pointing_size) < 1:
+            raise ValueError("surface_points and pointing_size must be >= 1")
+        geometry = dict(geometry or {})
+        unknown = sorted(set(geometry) - set(pointing_mod.GEOMETRY))
+        if unknown:
+            raise ValueError("geometry: unknown arguments %s" % ", ".join(unknown))
+        names, pairs = _split_meshes(meshes, lambda total: self._configure(total, int(cloud_points), "cloud_points", split, k_neighbors, batch_size,
+                                                                          shuffle, False, seed, device, drop_last))
+        self.surface_points, self.pointing_size, self.num_patches = int(surface_points), int(pointing_size), int(num_patches)
+        self.geometry, self.names, self._round, self._made = geometry, names, 0, {}
+        self.tables = surface.build_surface_tables(pairs, device=self.device, names=names)
+
+    def resample(self):
+        """Forget every mesh's surface cloud and pointing samples: the next use makes them from new draws."""
+        self._round += 1
+        self._made = {}
+        return self
+
+    def mesh_samples(self, m):
+        """``pointing.sample_fn_pointing``'s dict for mesh m of the split, made on first use."""
+        m = int(m)
+        if m not in self._made:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(((self.seed * 1000003 + self._round) * 1000003 + m + 500000003) & (2 ** 63 - 1))
+            made = pointing_mod.sample_fn_pointing(self.tables, m, self.surface_points, gen, self.pointing_size, **self.geometry)
+            if made["points"].shape[0] == 0:
+                raise ValueError("%s: no pointing sample (no candidate in the band)" % self.names[m])
+            self._made[m] = made
+        return self._made[m]
+
+    def _batch(self, idx, gen):
+        dev, n, P = self.device, self._n, self.num_patches
+        clouds, inputs, normals, cloud_idx, sample_idx, queries = [], [], [], [], [], []
+        for m in idx.tolist():
+            made = self.mesh_samples(m)
+            rows = torch.randint(made["surface"].shape[0], (n,), generator=gen, device=dev)
+            pick = torch.randint(made["points"].shape[0], (P,), generator=gen, device=dev)
+            cloud = made["surface"][rows]
+            q = made["points"][pick].float().double()
+            clouds.append(cloud)
+            inputs.append(seed_patches(cloud, q, self.k_neighbors))
+            normals.append(made["pointing"][pick].float())
+            cloud_idx.append(rows)
+            sample_idx.append(pick)
+            queries.append(q)
+        self.last_draws = {"cloud_idx": torch.stack(cloud_idx), "sample_idx": torch.stack(sample_idx), "queries": torch.stack(queries)}
+        return {"input": torch.stack(inputs), "normal": torch.stack(normals), "cloud": torch.stack(clouds), "index": idx}
+
+
+class FdSeedPatches(_DeviceLoader):
+    """fd's batches of the reference's folder route, from the meshes themselves: ``fd/transform.py:Subsamplerfd`` over
+    ``FdRayPatches.sample``.  A batch entry is a fresh run of the ray sampler on its mesh (``num_rays`` rays), a fresh surface sampling
+    of ``cloud_points`` points of the same mesh (``surface.sample_surface``) and ``num_patches`` of the kept rays, drawn with
+    replacement; the patches are centred on the rays' origins and turned so that the cast direction lies on +x
+    (``seed_patches(..., normals=directions)``): ``input`` f32 [B,P,k,3], ``len`` f32 [B,P], ``cloud`` f32 [B,cloud_points,3],
+    ``index``.  Every draw comes from the (seed, epoch, batch) generator, per entry the ray sampler's (``FdRayPatches``), then ``u``,
+    ``r1``, ``r2`` of the cloud, then the rays; ``last_draws`` holds ``ray_idx`` with the ``queries`` f64 [B,P,3] and ``directions``
+    f32 [B,P,3].  A mesh that is not watertight (unless ``allow_open``) or keeps no ray: ValueError."""
+
+    def __init__(self, meshes, num_rays=4096, cloud_points=2048, num_patches=16, k_neighbors=100, split="train", batch_size=4, shuffle=True,
+                 seed=0, device=None, drop_last=False, allow_open=False):
+        _seed_loader_checks(cloud_points, num_patches, k_neighbors)
+        if int(num_rays) < 1:
+            raise ValueError("num_rays must be >= 1")
+        # the shared checks first, on a stand-in count: the ray sampler's constructor below already builds tables on the device
+        self._configure(10, int(cloud_points), "cloud_points", split, k_neighbors, batch_size, shuffle, False, seed, device, drop_last)
+        self.rays = FdRayPatches(meshes, num_rays=num_rays, split=split, shuffle=False, seed=seed, device=device, allow_open=allow_open)
+        self._configure(len(self.rays), int(cloud_points), "cloud_points", "all", k_neighbors, batch_size, shuffle, False, seed, self.rays.device,
+                        drop_last)
+        self.split, self.num_patches, self.tables = split, int(num_patches), self.rays.tables
+
+    def _batch(self, idx, gen):
+        dev, n, P = self.device, self._n, self.num_patches
+        clouds, inputs, lens, ray_idx, queries, directions = [], [], [], [], [], []
+        for m in idx.tolist():
+            item = self.rays.sample(m, gen=gen)
+            if item["input"].shape[0] == 0:
+                raise ValueError("%s: the ray sampler kept no ray" % self.tables.names[m])
+            u = torch.rand((1, n), generator=gen, device=dev, dtype=torch.float64)
+            r1 = torch.rand((1, n), generator=gen, device=dev, dtype=torch.float64).float()
+            r2 = torch.rand((1, n), generator=gen, device=dev, dtype=torch.float64).float()
+            entry = torch.full((1,), m, dtype=torch.int64, device=dev)
+            cloud = surface.sample_surface(self.tables, entry, n, u, r1, r2, validate=False)[0][0]
+            pick = torch.randint(item["input"].shape[0], (P,), generator=gen, device=dev)
+            q, d = item["input"][pick].double(), item["normal"][pick].contiguous()
+            clouds.append(cloud)
+            inputs.append(seed_patches(cloud, q, self.k_neighbors, normals=d))
+            lens.append(item["len"][pick, 0])
+            ray_idx.append(pick)
+            queries.append(q)
+            directions.append(d)
+        self.last_draws = {"ray_idx": torch.stack(ray_idx), "queries": torch.stack(queries), "directions": torch.stack(directions)}
+        return {"input": torch.stack(inputs), "len": torch.stack(lens), "cloud": torch.stack(clouds), "index": idx}
